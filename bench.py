@@ -2,6 +2,15 @@
 effect NEM (BASELINE.json metric, config C3; C4 = the same per GPU at N > 1).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--path auto|stream|factored]
+                    [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and nothing else: it stages
+the model, warms up, times the K steps, writes the last step's outputs with
+--dump-outputs, and prints the result line.  --full adds everything else the
+line can carry: the launch-event cross-check of the kernel time, the C4
+chains, the streaming / fp64 / exact kernels on the same inputs, the fused
+MCMC step and the whole sampler, C5 and W128, and the CPU baselines
+(--no-extras / --no-cpu-baseline drop a part of it again).
 
 A step is one batched pass of the hot path over B = 2048 (pos, W)
 evaluations whose inputs are already resident in HBM, enqueued on one HIP
@@ -199,10 +208,12 @@ def stream_roofline(B, bpe, kern_ms, tr):
 
 
 def timed_steps(eng, torch, B, cap, steps, warmup, d_pos, d_w01, d_ll, stream, world, dist,
-                warmup_s=0.0, collective=None):
+                warmup_s=0.0, collective=None, launch_events=True):
     """``collective``: run the barriers and the best-score all-gather on the
     default process group (default: world > 1; rank-0-only extras pass
-    world = 1 and run none)."""
+    world = 1 and run none).  ``launch_events``: the library's per-launch
+    events on 20 more launches after the timed region (off: None is returned
+    in their place)."""
     coll = world > 1 if collective is None else collective
     def step():
         eng.score_dev(B, d_pos.data_ptr(), d_w01.data_ptr(), d_ll.data_ptr(), cap=cap, stream=stream)
@@ -248,6 +259,8 @@ def timed_steps(eng, torch, B, cap, steps, warmup, d_pos, d_w01, d_ll, stream, w
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
     kern_ms = ev0.elapsed_time(ev1) / steps
+    if not launch_events:
+        return wall, kern_ms, None
     eng.timing(True)
     for _ in range(20):
         step()
@@ -571,6 +584,17 @@ def wide_uncapped(torch, dist, stream, batch=2048, steps=5, warmup_s=0.3):
     return out
 
 
+def dump_outputs(path, ll, rank, world):
+    """--dump-outputs: what the timed path handed back in its last step -- the
+    order scores of the step's B evaluations (float64, one per evaluation) --
+    as ``ll.npy`` (``ll_rank<r>.npy`` per rank at N > 1).  The model, the
+    orders and the weights are seeded, so the same arguments give the same
+    inputs in every run and two builds compare output for output."""
+    os.makedirs(path, exist_ok=True)
+    name = "ll.npy" if world == 1 else f"ll_rank{rank}.npy"
+    np.save(os.path.join(path, name), np.ascontiguousarray(ll, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -581,14 +605,22 @@ def main():
     ap.add_argument("--batch", type=int, default=int(os.environ.get("NEMO_BENCH_BATCH", 2048)))
     ap.add_argument("--path", default=os.environ.get("NEMO_BENCH_PATH", "auto"), choices=list(PATHS))
     ap.add_argument("--config", default="C3")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the stream-kernel, MCMC and C4 lines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's order scores to DIR/ll.npy (float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: the launch-event cross-check, the stream-kernel, fp64, exact, "
+                         "MCMC, C4, C5 and W128 lines and the CPU baselines")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip the stream-kernel, MCMC and C4 lines")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--cpu-procs", type=int, default=8,
                     help="processes of the multi-process CPU baseline (1: off)")
     ap.add_argument("--c4-chains", type=int, default=128, help="C4: chains over all ranks (0: off)")
     ap.add_argument("--c4-steps", type=int, default=30, help="C4: timed MCMC steps (after 2 untimed ones)")
     args = ap.parse_args()
+    extras_on = args.full and not args.no_extras
+    cpu_on = args.full and not args.no_cpu_baseline
 
     import torch
     import torch.distributed as dist
@@ -633,15 +665,18 @@ def main():
     stream = side.cuda_stream
 
     wall, kern_ms, launch_ev_ms = timed_steps(eng, torch, B, cap, args.steps, args.warmup, d_pos, d_w01,
-                                              d_ll, stream, world, dist, warmup_s=args.warmup_seconds)
+                                              d_ll, stream, world, dist, warmup_s=args.warmup_seconds,
+                                              launch_events=args.full)
     t_max = torch.tensor([wall], dtype=torch.float64, device="cuda" if backend == "nccl" else "cpu")
     if world > 1:
         dist.all_reduce(t_max, op=dist.ReduceOp.MAX)
     t_max = float(t_max.item())
     ll = d_ll.cpu().numpy()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, ll, rank, world)
 
     extras = {}
-    if not args.no_extras and args.c4_chains > 0 and args.config == "C3":
+    if extras_on and args.c4_chains > 0 and args.config == "C3":
         # BASELINE C4 on every rank: the chains sharded over the ranks, one
         # ChainBatch per rank, one all-gather of (best score, best order) --
         # over RCCL with device tensors at N > 1 on GPUs
@@ -658,7 +693,7 @@ def main():
             "accepted": None,
             "reference_cpu_s_per_chain_step": 1.2}
 
-    if rank == 0 and not args.no_extras:
+    if rank == 0 and extras_on:
         # the generic streaming kernel on the same model (HBM-priced roofline)
         eng.set_option("score_path", 1)
         Bs = min(B, 128)
@@ -871,7 +906,7 @@ def main():
             "ll_sample": float(ll[0]),
         }
         rec.update(extras)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and cpu_on:
             rec["cpu_baseline"] = cpu_baseline(m, args.cpu_seconds, args.config)
             rec["cpu_baseline"]["host_nproc"] = os.cpu_count()
             rec["cpu_baseline"]["host_cpu"] = host_cpu()

@@ -90,6 +90,58 @@ def test_cpu_baseline_procs_plumbing():
     assert r["cores"] == 2 and r["kind"] == "port" and r["value"] > 0
 
 
+def test_dump_outputs_writes_the_scores_as_float64(tmp_path):
+    import numpy as np
+    ll = np.array([-1.5, -2.25, -3.0])
+    bench.dump_outputs(str(tmp_path / "d"), ll, 0, 1)
+    got = np.load(tmp_path / "d" / "ll.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, ll)
+    bench.dump_outputs(str(tmp_path / "d"), ll, 1, 2)   # N > 1: one file per rank
+    assert np.array_equal(np.load(tmp_path / "d" / "ll_rank1.npy"), ll)
+
+
+@pytest.mark.gpu
+def test_plain_run_is_the_headline_alone_and_dumps_its_last_step(tmp_path):
+    """A plain run (C2, two steps): the result line with its headline fields and
+    none of --full's; --dump-outputs holds the step's B order scores, float64,
+    of the seeded inputs: the oracle (numpy, on the host) scores the same
+    evaluations within 1e-6, smoke()'s bound (the kernels' error budget is
+    1e-7).  The run is a child process; this one does no GPU work."""
+    import json
+    import subprocess
+
+    import numpy as np
+    from scipy.special import expit
+    d = tmp_path / "out"
+    res = subprocess.run([sys.executable, os.path.join(HERE, "bench.py"), "--gpus", "1", "--steps", "2",
+                          "--warmup", "1", "--warmup-seconds", "0", "--config", "C2", "--batch", "64",
+                          "--dump-outputs", str(d)], capture_output=True, text=True, timeout=120)
+    assert res.returncode == 0, res.stderr[-2000:]
+    rec = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1])
+    assert rec["steps"] == 2 and rec["ms_per_step"] > 0 and rec["value"] > 0 and rec["unit"] == "evals/s"
+    assert abs(rec["value"] - 64 * 1e3 / rec["ms_per_step"]) <= 1e-9 * rec["value"]
+    for key in ("metric", "higher_is_better", "dtype", "roofline"):
+        assert key in rec
+    for key in ("cpu_baseline", "cpu_baseline_procs", "stream_kernel", "c4_chains", "mcmc_fused_step"):
+        assert key not in rec
+    assert os.listdir(d) == ["ll.npy"]
+    ll = np.load(d / "ll.npy")
+    assert ll.dtype == np.float64 and ll.shape == (64,) and ll[0] == rec["ll_sample"]
+    # the run's inputs, drawn again from its seeds
+    for p in (os.path.join(HERE, "nem-mcmc-optimization_amd"), os.path.join(HERE, "oracle")):
+        if p not in sys.path:
+            sys.path.insert(0, p)
+    import nemo_oracle as no
+    from nemo import generator
+    m = generator.config_nem("C2")
+    t = m.get_score_tensor()
+    rng = np.random.default_rng(1000)
+    pos = np.array([rng.permutation(m.num_s) for _ in range(64)], dtype=np.int32)
+    w01 = expit(rng.uniform(-3, 3, (64, m.num_s, m.num_s)))
+    for c in range(0, 64, 8):
+        assert abs(ll[c] - no.order_score(m.U, t, np.argsort(pos[c]), w01[c])) <= 1e-6, c
+
+
 def test_stream_roofline_is_a_hardware_fraction():
     # the streaming kernel's algorithmic bytes exceed HBM's (the table is
     # Infinity-Cache resident and re-read across the batch): priced against

@@ -7,4 +7,4 @@ for n in 16 128; do
     echo "== n=$n $tag"; python tools/exact_pmc.py "$P/pmc_${n}_$tag/p_counter_collection.csv"
   done
 done
-timeout -k 10 600 python bench.py > $P/bench.json 2> $P/bench.err; rc=$?; tail -c 3000 $P/bench.json; exit $rc
+timeout -k 10 600 python bench.py --full > $P/bench.json 2> $P/bench.err; rc=$?; tail -c 3000 $P/bench.json; exit $rc

@@ -3,7 +3,7 @@
 # 16 and 128 chains (each counter set in its own pass)
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 R=$(pwd); P=gpurun_out/r6d; mkdir -p $P; export TMPDIR=/tmp PYTHONUNBUFFERED=1
-timeout -k 10 400 python bench.py --no-cpu-baseline > $P/bench.log 2>&1 || { tail -5 $P/bench.log; exit 1; }
+timeout -k 10 400 python bench.py --full --no-cpu-baseline > $P/bench.log 2>&1 || { tail -5 $P/bench.log; exit 1; }
 grep '^{' $P/bench.log > $P/bench.json
 python -c "
 import json; d=json.load(open('$P/bench.json'))

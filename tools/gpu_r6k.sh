@@ -6,7 +6,7 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -x -q -rf --timeout 120 --tim
 rc=$?; echo "pytest rc=$rc"; tail -3 $P/pytest_gpu.log; [ $rc -eq 0 ] || exit $rc
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $P/smoke.log 2>&1 || { tail -5 $P/smoke.log; exit 1; }
 tail -1 $P/smoke.log
-timeout -k 10 600 python bench.py > $P/bench.log 2>&1 || { tail -5 $P/bench.log; exit 1; }
+timeout -k 10 600 python bench.py --full > $P/bench.log 2>&1 || { tail -5 $P/bench.log; exit 1; }
 grep '^{' $P/bench.log > $P/bench.json
 python -c "
 import json; d=json.load(open('$P/bench.json'))

@@ -13,9 +13,9 @@ if [ -z "$SKIP_TESTS" ]; then
   TAILN=6 step pytest_gpu 1000 python -u -m pytest tests -m gpu -q -rf --timeout 120 --timeout-method thread ${PYTEST_ARGS} || exit 1
 fi
 B=${NEMO_BENCH_BATCH:-2048}
-TAILN=2 step bench_traced 420 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/$P/trace" -o t -- python "$R/bench.py" || exit 1
+TAILN=2 step bench_traced 420 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/$P/trace" -o t -- python "$R/bench.py" --full || exit 1
 grep '^{' "$P/bench_traced.log" > "$P/bench_traced.json"
-TAILN=1 step bench 300 python bench.py || exit 1
+TAILN=1 step bench 300 python bench.py --full || exit 1
 grep '^{' "$P/bench.log" > "$P/bench.json"
 if [ -n "$PMC" ]; then
   TAILN=2 step fetch 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$R/$P/fetch" -o f -- python "$R/bench.py" --steps 5 --warmup 1 --no-cpu-baseline --no-extras --warmup-seconds 0 --batch $B || exit 1

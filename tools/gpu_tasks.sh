@@ -53,9 +53,9 @@ done
 # n_gathered must be 128 and the gathered scores (sha) identical.
 task_c4_rehearsal() (
 P=${PROF_DIR:-gpurun_out/c4}; mkdir -p "$P"; export TMPDIR=/tmp PYTHONUNBUFFERED=1
-timeout -k 10 300 python bench.py --steps 10 --warmup 2 --no-cpu-baseline --c4-steps 10 > "$P/n1.json" 2> "$P/n1.err" || exit $?
+timeout -k 10 300 python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --c4-steps 10 > "$P/n1.json" 2> "$P/n1.err" || exit $?
 NEMO_BENCH_BACKEND=gloo timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-    --master-addr 127.0.0.1 --master-port 29512 bench.py --gpus 2 --steps 10 --warmup 2 --c4-steps 10 \
+    --master-addr 127.0.0.1 --master-port 29512 bench.py --full --gpus 2 --steps 10 --warmup 2 --c4-steps 10 \
     > "$P/n2.json" 2> "$P/n2.err" || exit $?
 python - "$P" <<'PY'
 import json, sys
