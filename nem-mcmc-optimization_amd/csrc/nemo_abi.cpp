@@ -231,7 +231,7 @@ int nemo_reserve(nemo_ctx* ctx, int max_batch, int max_chains) {
     HIPCHK(dalloc(&c.d_fperm, nb * sp));
     HIPCHK(dalloc(&c.d_fpartial, nb * (size_t)nemo::factored_partials(c)));
     c.cap_batch = nb;
-    if (c.fact_kernel == 20) HIPCHK(nemo::i8img_reserve(c));
+    if (nemo::host::kFactKernels[c.fact_kernel].split) HIPCHK(nemo::i8img_reserve(c));
   }
   const int nc = std::max(max_chains, 1);
   if (nc > c.cap_chains) {
@@ -653,7 +653,7 @@ int nemo_score(nemo_ctx* ctx, int batch, const int32_t* pos, const double* w01, 
     const hipError_t e = nemo::launch_score_factored(c, batch, cap, (const int32_t*)ds, (const double*)(ds + o_w01),
                                                      (double*)(ds + o_ll), nullptr, nullptr, nullptr, st, false, &np);
     c.part_out = nullptr;
-    HIPCHK(e);  // np <= npart: launch_score_factored checks score_partials before launching
+    HIPCHK(e);  // np <= npart: launch_score_factored checks the variant's partial count before launching
     HIPCHK(hipMemcpyAsync(hs + o_part, ds + o_part, total - o_part, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     if (np > 0) {
@@ -1537,10 +1537,12 @@ int nemo_set_option(nemo_ctx* ctx, const char* name, int value) {
     return NEMO_OK;
   }
   if (strcmp(name, "fact_kernel") == 0) {
-    if (value < 0 || value > 20) return fail(NEMO_ERR_ARG, "fact_kernel=%d not in 0..20", value);
+    constexpr int kMax = nemo::host::kFactKernelMax;
+    if (value < 0 || value > kMax) return fail(NEMO_ERR_ARG, "fact_kernel=%d not in 0..%d", value, kMax);
     ctx->c.fact_kernel = value;
-    if (value == 20) return nemo::i8img_reserve(ctx->c) == hipSuccess ? NEMO_OK
-                                                                      : fail(NEMO_ERR_HIP, "fact_kernel 20: image buffer");
+    if (nemo::host::kFactKernels[value].split)
+      return nemo::i8img_reserve(ctx->c) == hipSuccess ? NEMO_OK
+                                                       : fail(NEMO_ERR_HIP, "fact_kernel %d: image buffer", value);
     return NEMO_OK;
   }
   if (strcmp(name, "local_prod") == 0) {

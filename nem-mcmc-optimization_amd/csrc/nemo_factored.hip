@@ -93,10 +93,6 @@ __device__ __forceinline__ double vmax(double a, double b) {
 // U[S][e] + kPadG, whose exp underflows to exactly 0 next to any real row
 constexpr double kPadG = -1.0e6;
 
-// tiles per wave of the pipelined kernel: fixed, so the tile -> wave ->
-// partial assignment (hence every bit of ll) does not depend on the batch
-constexpr int kPipeTilesPerWave = 8;
-
 __device__ __forceinline__ int fxcd_work_index(int L, int N, int remap) {
   if (!remap) return L;
   const int x = L & 7, k = L >> 3;
@@ -553,77 +549,24 @@ hipError_t launch_pipe_t(Ctx& c, int batch, hipStream_t st, int* nparts) {
 
 }  // namespace
 
-int factored_spad(int S) {
-  const int nr = (S + 15) / 16;
-  const int sizes[] = {1, 2, 4, 8, 16};
-  for (int v : sizes)
-    if (nr <= v) return v * 16;
-  return -1;
+// ---- the variant of a call: adapters of nemo_fact_kernels.h over Ctx ----
+static host::FactModel fact_model(const Ctx& c, int cap) {
+  auto bnd = [&](int kind) { return host::fixed_point_bound(kind, c.i8_cexp, c.fx_colsum, c.S, c.E, cap); };
+  return {c.S, c.E, c.fspad, c.nwords, c.d_B8 != nullptr, c.i8o_ok, c.i8l_ok, c.i8w_ok, c.win_ok,
+          bnd(host::kFxLog2), bnd(host::kFxNatural), c.err_budget};
 }
 
-int factored_partials(const Ctx& c) {
-  // chunked: one per wave slot of the 128-effect blocks; pipelined: one per
-  // wave of ceil(tiles / (8 * waves)) blocks, waves in {4, 8}
-  const int cols = kFactWaves * 16;
-  const int nt = (c.E + 15) / 16;
-  int n = ((c.E + cols - 1) / cols) * kFactWaves;
-  for (int wv : {4, 8}) n = std::max(n, ((nt + kPipeTilesPerWave * wv - 1) / (kPipeTilesPerWave * wv)) * wv);
-  return std::max(n, (c.E + 63) / 64);  // the lookup-table kernel: one per word
-}
+int factored_partials(const Ctx& c) { return host::fact_partials_max(c.E); }
 
-int score_partials(const Ctx& c, int fk) {
-  const int nt = (c.E + 15) / 16;
-  if (fk == 9 || fk == 15) return c.nwords;                        // launch_score_window
-  if (fk == 18 || fk == 19) return (nt + kWideSetT - 1) / kWideSetT;  // launch_i8w_t
-  if (fk >= 4) return (nt + 7) / 8;                                 // launch_i8_t / i8o_t / i8l_t / i8s / i8p
-  if (fk == 2 || fk == 3) {                                         // launch_pipe_t
-    const int wv = fk == 3 ? 8 : 4, tpb = kPipeTilesPerWave * wv;
-    return ((nt + tpb - 1) / tpb) * wv;
-  }
-  const int cols = kFactWaves * 16;                                 // launch_fact_w
-  return ((c.E + cols - 1) / cols) * kFactWaves;
-}
+int score_partials(const Ctx& c, int fk) { return host::fact_partials(host::kFactKernels[fk], c.E, c.nwords); }
 
 int resolve_fact_kernel(const Ctx& c, int cap, bool ll_only, double* bound) {
   if (bound) *bound = 0.0;
   if (!c.factored) return -1;
-  if (cap >= c.S - 1) cap = 0;  // every predecessor is within the cap: no cap (same bits)
-  // the int8 kernels: S <= 64, ll only (they write no cs / cells / order weights)
-  const bool i8cap = c.fspad <= 64 && c.d_B8 && ll_only;
-  const bool wincap = ll_only && c.win_ok && cap >= 1 && cap <= kWinMaxCap;
-  auto bnd = [&](int kind) { return host::fixed_point_bound(kind, c.i8_cexp, c.fx_colsum, c.S, c.E, cap); };
-  // the log2 kernel for 64 < S <= 128 (score_i8w_kernel)
-  const bool i8wcap = c.fspad == 128 && c.i8w_ok && c.d_B8 && ll_only;
-  int fk = c.fact_kernel;
-  if (fk == 0) {
-    // auto: the capped lookup-table kernel for capped calls; else the fastest
-    // int8 kernel whose worst-case ll error (nemo_host.h) stays within
-    // err_budget -- log2 fixed point (10; 18 for S > 64), natural units (8),
-    // max offset (4) -- else the fp64 MFMA kernels
-    if (wincap) fk = 9;
-    else if (i8wcap && bnd(host::kFxLog2) <= c.err_budget) fk = 18;
-    else if (!i8cap) fk = 1;
-    else if (c.i8o_ok && c.i8l_ok && bnd(host::kFxLog2) <= c.err_budget) fk = 10;
-    else if (c.i8o_ok && bnd(host::kFxNatural) <= c.err_budget) fk = 8;
-    else if (!c.i8o_ok && bnd(host::kFxNatural) <= c.err_budget) fk = 4;
-    else fk = 2;
-  } else if (fk == 18 || fk == 19) {
-    if (!ll_only || c.fspad != 128) fk = 1;
-    else if (!i8wcap) return -1;
-  } else if (fk == 9 || fk == 15) {
-    if (!wincap) return -1;
-  } else if (fk == 2 || fk == 3) {
-    if (!(ll_only && c.fspad <= 64)) fk = 1;
-  } else if (fk >= 4) {
-    if (!i8cap) fk = 1;  // an int8 kernel asked for a call it cannot serve: chunked fp64
-    else if ((fk == 7 || fk == 8) && !c.i8o_ok) return -1;
-    else if (fk >= 10 && !(c.i8o_ok && c.i8l_ok)) return -1;
-  }
-  if (bound) {
-    const bool l2 = fk >= 10 && fk != 15, nat = fk >= 4 && fk <= 8;  // (18: log2, S > 64)
-    *bound = l2 ? bnd(host::kFxLog2) : nat ? bnd(host::kFxNatural) : 0.0;
-  }
-  return fk;
+  const host::FactModel m = fact_model(c, cap);
+  const host::FactChoice ch = host::resolve_fact(m, c.fact_kernel, cap, ll_only, 0);  // (the batch only shapes the row)
+  if (bound && ch.fk >= 0) *bound = host::fact_bound(ch.k, m);
+  return ch.fk;
 }
 
 hipError_t launch_score_factored(Ctx& c, int batch, int cap, const int32_t* d_pos,
@@ -632,31 +575,16 @@ hipError_t launch_score_factored(Ctx& c, int batch, int cap, const int32_t* d_po
   const int spad = c.fspad;
   if (cap >= c.S - 1) cap = 0;  // every predecessor is within the cap: no cap (same bits)
   const bool ll_only = !d_cs && !d_cells && !d_ow;
-  // option fact_kernel: 0 auto (resolve_fact_kernel), 1 chunked, 2 / 3 f64
-  // pipelined with 4 / 8 waves per block, 4 / 5 int8 with 4 / 5 digit pairs,
-  // 6 int8 (4 pairs) with 8 waves, 7 / 8 int8 with the offset log-sum-exp
-  // (4 / 8 waves), 9 / 15 the capped lookup-table kernel (15: its round-1
-  // form), 10 / 11 the offset kernel in log2 fixed point (8 / 4 waves; 12: 16
-  // waves; 13: register-stationary; 14: 8 waves compiled for 6 waves per
-  // SIMD; 10 walks two effect tiles per iteration, 16 is the same kernel with
-  // one; 17: 10's walk in persistent blocks that prep the next evaluation
-  // during the walk; 18 / 19 the log2 kernel for 64 < S <= 128 with two / one
-  // tiles per iteration; 20: 10 as a prep-only and a walk-only launch)
-  const int fk = resolve_fact_kernel(c, cap, ll_only, nullptr);
-  if (fk < 0) return hipErrorInvalidValue;  // asked for a kernel the staged model does not support
+  if (!c.factored) return hipErrorInvalidValue;
+  const host::FactChoice ch = host::resolve_fact(fact_model(c, cap), c.fact_kernel, cap, ll_only, batch);
+  if (ch.fk < 0) return hipErrorInvalidValue;  // asked for a kernel the staged model does not support
+  const host::FactKernel& k = ch.k;
   // every partial buffer (d_fpartial, a redirected part_out) holds
   // factored_partials per evaluation: checked before anything is launched
-  const int np_pred = score_partials(c, fk);
+  const int np_pred = host::fact_partials(k, c.E, c.nwords);
   if (np_pred > factored_partials(c)) return hipErrorInvalidValue;
-  const bool is_auto = c.fact_kernel == 0;
-  const bool win = fk == 9 || fk == 15;
-  const bool wide = fk == 18 || fk == 19;
-  const bool l2 = fk >= 10 && fk != 15 && !wide;
-  const bool i8o = fk == 7 || fk == 8 || l2;
-  const bool i8 = fk >= 4 && fk <= 6;
-  const bool pipe = fk == 2 || fk == 3;
   hipError_t err = hipSuccess;
-  if (!i8 && !i8o && !win && !wide && !prepped) {  // the int8 and lookup-table kernels derive their inputs themselves
+  if (!k.self_prep && !prepped) {  // the int8 and lookup-table kernels derive their inputs themselves
     prep_factored_kernel<<<batch * (spad / 4), 256, 0, st>>>(c.S, spad, cap, d_pos, d_w01, c.d_elo,
                                                              c.d_ehi, c.d_fDp, c.d_fG, c.d_fperm);
     err = hipGetLastError();
@@ -670,48 +598,50 @@ hipError_t launch_score_factored(Ctx& c, int batch, int cap, const int32_t* d_po
   }
   int np = 0;
   bool finalized = false;
-  if (win) {
-    err = launch_score_window(c, batch, cap, d_pos, d_w01, d_ll, st, &np, &finalized, fk == 15);
-  } else if (wide) {
-    err = launch_score_i8w(c, batch, cap, d_pos, d_w01, d_ll, fk == 18, st, &np, &finalized);
-  } else if (i8o) {
-    // 7 / 8: offset log-sum-exp with 4 / 8 waves per block; 10 (auto's l2
-    // choice): 8 waves, two effect tiles per iteration; 11: 4 waves; 12: 16;
-    // 16: 8 waves, one tile per iteration
-    const int waves = fk == 20 ? -20 : fk == 17 ? -3 : fk == 13 ? 0 : fk == 14 ? -8 : fk == 16 ? 8 : fk == 12 ? 16
-                    : (fk == 7 || fk == 11) ? 4 : fk == 10 ? -2 : 8;
-    err = launch_score_i8o(c, batch, cap, d_pos, d_w01, d_ll, waves, l2, st, &np, &finalized);
-  } else if (i8) {
-    // auto: 4 waves per block for large batches, 8 (fewer splits) below
-    const int waves = fk == 6 ? 8 : (fk == 4 && is_auto && batch < 384 ? 8 : 4);
-    err = launch_score_i8(c, batch, cap, d_pos, d_w01, d_ll, fk == 5 ? 5 : 4, waves, st, &np,
-                          &finalized);
-  } else if (pipe) {
-    const bool w8 = fk == 3;
-    switch (spad / 16) {
+  using host::FactFamily;
+  switch (k.family) {
+    case FactFamily::kWindow:
+      err = launch_score_window(c, batch, cap, d_pos, d_w01, d_ll, st, &np, &finalized, k.round1);
+      break;
+    case FactFamily::kI8w:
+      err = launch_score_i8w(c, batch, cap, d_pos, d_w01, d_ll, k.tiles == 2, st, &np, &finalized);
+      break;
+    case FactFamily::kI8o:
+    case FactFamily::kI8l:
+    case FactFamily::kI8s:
+    case FactFamily::kI8p:
+      err = launch_score_i8o(c, batch, cap, d_pos, d_w01, d_ll, k, st, &np, &finalized);
+      break;
+    case FactFamily::kI8:
+      err = launch_score_i8(c, batch, cap, d_pos, d_w01, d_ll, k, st, &np, &finalized);
+      break;
+    case FactFamily::kPipe:
+      switch (spad / 16) {
 #define NEMO_PIPE(NRV)                                                               \
   case NRV:                                                                          \
-    err = w8 ? launch_pipe_t<NRV, 8>(c, batch, st, &np)                              \
-             : launch_pipe_t<NRV, 4>(c, batch, st, &np);                             \
+    err = k.waves == 8 ? launch_pipe_t<NRV, 8>(c, batch, st, &np)                    \
+                       : launch_pipe_t<NRV, 4>(c, batch, st, &np);                   \
     break;
-      NEMO_PIPE(1)
-      NEMO_PIPE(2)
-      NEMO_PIPE(4)
+        NEMO_PIPE(1)
+        NEMO_PIPE(2)
+        NEMO_PIPE(4)
 #undef NEMO_PIPE
-      default: return hipErrorInvalidValue;
-    }
-  } else {
-    switch (spad / 16) {
-      case 1: err = launch_fact_t<1>(c, batch, cap, d_cs, d_cells, d_ow, st, &np); break;
-      case 2: err = launch_fact_t<2>(c, batch, cap, d_cs, d_cells, d_ow, st, &np); break;
-      case 4: err = launch_fact_t<4>(c, batch, cap, d_cs, d_cells, d_ow, st, &np); break;
-      case 8: err = launch_fact_t<8>(c, batch, cap, d_cs, d_cells, d_ow, st, &np); break;
-      case 16: err = launch_fact_t<16>(c, batch, cap, d_cs, d_cells, d_ow, st, &np); break;
-      default: return hipErrorInvalidValue;
-    }
+        default: return hipErrorInvalidValue;
+      }
+      break;
+    case FactFamily::kChunked:
+      switch (spad / 16) {
+        case 1: err = launch_fact_t<1>(c, batch, cap, d_cs, d_cells, d_ow, st, &np); break;
+        case 2: err = launch_fact_t<2>(c, batch, cap, d_cs, d_cells, d_ow, st, &np); break;
+        case 4: err = launch_fact_t<4>(c, batch, cap, d_cs, d_cells, d_ow, st, &np); break;
+        case 8: err = launch_fact_t<8>(c, batch, cap, d_cs, d_cells, d_ow, st, &np); break;
+        case 16: err = launch_fact_t<16>(c, batch, cap, d_cs, d_cells, d_ow, st, &np); break;
+        default: return hipErrorInvalidValue;
+      }
+      break;
   }
   if (err != hipSuccess) return err;
-  if (np != np_pred) return hipErrorUnknown;  // score_partials out of step with a launcher: a build bug
+  if (np != np_pred) return hipErrorUnknown;  // the row's partial rule out of step with its launcher: a build bug
   if (e1) {
     (void)hipEventRecord(e1, st);
     c.launches++;

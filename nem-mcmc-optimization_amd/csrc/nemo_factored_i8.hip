@@ -642,12 +642,8 @@ hipError_t launch_i8_t(Ctx& c, int batch, int cap, const int32_t* d_pos, const d
 // constant per 8-tile set (fixed order), the logs run once per set on
 // prod(l) kept as mantissa * 2^lexp.
 // ---------------------------------------------------------------------------
-#ifndef NEMO_I8O_WAVES_PER_SIMD
-#define NEMO_I8O_WAVES_PER_SIMD 4
-#endif
-#ifndef NEMO_I8L2_OCC  // waves per SIMD the two-tile log2 kernel is compiled for
-#define NEMO_I8L2_OCC 4
-#endif
+// (NEMO_I8O_WAVES_PER_SIMD, NEMO_I8L2_OCC: the waves per SIMD these kernels
+// are compiled for, nemo_fact_kernels.h)
 
 // acc + e^x for |x| <= 700: 2^(k/2048) e^r, k = rint(x 2048/ln2), |r| <=
 // ln2/4096, degree-3 series (error r^4/24 < 4e-17).  The rounding constant is
@@ -1709,7 +1705,7 @@ hipError_t launch_i8l_t(Ctx& c, int batch, int cap, const int32_t* d_pos, const 
   int split = (slots + batch - 1) / batch;
   split = split < 1 ? 1 : (split > nsets ? nsets : split);
   const size_t lds = kExpTabN * 8 + 128 * 16 + 3 * SPAD * 8 + 3 * SPAD * 4 + (size_t)7 * SPAD * 64;
-  if (SPLIT) {  // fact_kernel 20: a prep-only launch (one block per evaluation), then the walks
+  if (SPLIT) {  // a prep-only launch (one block per evaluation), then the walks
     if (!c.d_i8img || c.i8img_cap < batch || (size_t)SPAD * 460 != i8img_bytes(c.fspad))
       return hipErrorInvalidValue;
     score_i8l_kernel<NR, WAVES, OCC, TT, 1><<<dim3(batch), WAVES * kWave, lds, st>>>(
@@ -2071,34 +2067,40 @@ hipError_t i8img_reserve(Ctx& c) {
   return e;
 }
 
+// the instantiation of row k (families kI8o, kI8l, kI8s, kI8p)
 hipError_t launch_score_i8o(Ctx& c, int batch, int cap, const int32_t* d_pos, const double* d_w01,
-                            double* d_ll, int waves, bool l2, hipStream_t st, int* nparts,
+                            double* d_ll, const host::FactKernel& k, hipStream_t st, int* nparts,
                             bool* finalized) {
+  using host::FactFamily;
   if (!c.i8o_ok || !c.d_Uoff || !c.d_nullsum || !c.d_B8 || !c.d_i8o_tabs) return hipErrorInvalidValue;
-  if (l2 && (!c.i8l_ok || !c.d_udig2)) return hipErrorInvalidValue;
+  if (k.family != FactFamily::kI8o && (!c.i8l_ok || !c.d_udig2)) return hipErrorInvalidValue;
+  const bool diag = c.i8o_diag && !c.i8o_nodiag;
+#define NEMO_ARGS c, batch, cap, d_pos, d_w01, d_ll, st, nparts, finalized
+#define NEMO_I8L(NRV, WV, OCC, TT, SPLIT)                                                                  \
+  if (k.family == FactFamily::kI8l && k.waves == WV && k.occ == OCC && k.tiles == TT && k.split == SPLIT)  \
+    return launch_i8l_t<NRV, WV, OCC, TT, SPLIT>(NEMO_ARGS);
+#define NEMO_I8O(NRV)                                                                                      \
+  case NRV:                                                                                                \
+    if (k.family == FactFamily::kI8s) return launch_i8s_t<NRV>(NEMO_ARGS);                                 \
+    NEMO_I8L(NRV, 16, NEMO_I8O_WAVES_PER_SIMD, 1, false)                                                   \
+    if (k.family == FactFamily::kI8p) return launch_i8p_t<NRV>(NEMO_ARGS);                                 \
+    NEMO_I8L(NRV, 8, NEMO_I8O_WAVES_PER_SIMD, 1, false)                                                    \
+    NEMO_I8L(NRV, 8, 6, 1, false)                                                                          \
+    NEMO_I8L(NRV, 8, NEMO_I8L2_OCC, 2, false)                                                              \
+    NEMO_I8L(NRV, 8, NEMO_I8L2_OCC, 2, true)                                                               \
+    NEMO_I8L(NRV, 4, NEMO_I8O_WAVES_PER_SIMD, 1, false)                                                    \
+    if (k.family != FactFamily::kI8o) return hipErrorInvalidValue;                                         \
+    if (diag) return k.waves == 8 ? launch_i8o_t<NRV, 8, true>(NEMO_ARGS) : launch_i8o_t<NRV, 4, true>(NEMO_ARGS); \
+    return k.waves == 8 ? launch_i8o_t<NRV, 8, false>(NEMO_ARGS) : launch_i8o_t<NRV, 4, false>(NEMO_ARGS);
   switch (c.fspad / 16) {
-#define NEMO_I8O(NRV)                                                                          \
-  case NRV:                                                                                    \
-    if (l2)                                                                                    \
-      return waves == 0 ? launch_i8s_t<NRV>(c, batch, cap, d_pos, d_w01, d_ll, st, nparts, finalized) \
-           : waves == 16 ? launch_i8l_t<NRV, 16>(c, batch, cap, d_pos, d_w01, d_ll, st, nparts, finalized) \
-           : waves == -3 ? launch_i8p_t<NRV>(c, batch, cap, d_pos, d_w01, d_ll, st, nparts, finalized) \
-           : waves == 8  ? launch_i8l_t<NRV, 8>(c, batch, cap, d_pos, d_w01, d_ll, st, nparts, finalized)  \
-           : waves == -8 ? launch_i8l_t<NRV, 8, 6>(c, batch, cap, d_pos, d_w01, d_ll, st, nparts, finalized) \
-           : waves == -2 ? launch_i8l_t<NRV, 8, NEMO_I8L2_OCC, 2>(c, batch, cap, d_pos, d_w01, d_ll, st, nparts, finalized) \
-           : waves == -20 ? launch_i8l_t<NRV, 8, NEMO_I8L2_OCC, 2, true>(c, batch, cap, d_pos, d_w01, d_ll, st, nparts, finalized) \
-                         : launch_i8l_t<NRV, 4>(c, batch, cap, d_pos, d_w01, d_ll, st, nparts, finalized); \
-    if (c.i8o_diag && !c.i8o_nodiag)                                                           \
-      return waves == 8 ? launch_i8o_t<NRV, 8, true>(c, batch, cap, d_pos, d_w01, d_ll, st, nparts, finalized) \
-                        : launch_i8o_t<NRV, 4, true>(c, batch, cap, d_pos, d_w01, d_ll, st, nparts, finalized); \
-    return waves == 8 ? launch_i8o_t<NRV, 8, false>(c, batch, cap, d_pos, d_w01, d_ll, st, nparts, finalized) \
-                      : launch_i8o_t<NRV, 4, false>(c, batch, cap, d_pos, d_w01, d_ll, st, nparts, finalized);
     NEMO_I8O(1)
     NEMO_I8O(2)
     NEMO_I8O(4)
-#undef NEMO_I8O
     default: return hipErrorInvalidValue;
   }
+#undef NEMO_I8O
+#undef NEMO_I8L
+#undef NEMO_ARGS
 }
 
 template <bool TWO>
@@ -2121,7 +2123,7 @@ hipError_t launch_i8w_t(Ctx& c, int batch, int cap, const int32_t* d_pos, const 
   return hipGetLastError();
 }
 
-// fact_kernel 18: two tiles per iteration (auto); 19: one
+// two: two tiles per iteration (auto's pick), else one
 hipError_t launch_score_i8w(Ctx& c, int batch, int cap, const int32_t* d_pos, const double* d_w01,
                             double* d_ll, bool two, hipStream_t st, int* nparts, bool* finalized) {
   return two ? launch_i8w_t<true>(c, batch, cap, d_pos, d_w01, d_ll, st, nparts, finalized)
@@ -2320,12 +2322,12 @@ hipError_t stage_i8o(Ctx& c, const std::vector<double>& elo, const std::vector<d
 }
 
 hipError_t launch_score_i8(Ctx& c, int batch, int cap, const int32_t* d_pos, const double* d_w01,
-                           double* d_ll, int np, int waves, hipStream_t st, int* nparts,
+                           double* d_ll, const host::FactKernel& k, hipStream_t st, int* nparts,
                            bool* finalized) {
   const int nr = c.fspad / 16;
   if (c.fspad > 64 || !c.d_B8) return hipErrorInvalidValue;
 #define NEMO_I8(NRV, WV, NPV)                \
-  if (nr == NRV && waves == WV && np == NPV) \
+  if (nr == NRV && k.waves == WV && k.pairs == NPV) \
     return launch_i8_t<NRV, WV, NPV>(c, batch, cap, d_pos, d_w01, d_ll, st, nparts, finalized);
   NEMO_I8(1, 4, 4) NEMO_I8(2, 4, 4) NEMO_I8(4, 4, 4)
   NEMO_I8(1, 4, 5) NEMO_I8(2, 4, 5) NEMO_I8(4, 4, 5)

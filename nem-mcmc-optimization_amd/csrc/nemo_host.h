@@ -1,7 +1,8 @@
 // nemo_host.h -- the host logic of the C-ABI that needs no HIP: argument
 // checks, the worst-case error bounds of the fixed-point score kernels, the
-// level schedule of InverseMethod's pair loop and the queue of asynchronous
-// fused steps.  Header-only so that tests/host/host_check.cpp builds it with
+// level schedule of InverseMethod's pair loop, the queue of asynchronous
+// fused steps and (nemo_fact_kernels.h) the table of factored score-kernel
+// variants.  Header-only so that tests/host/host_check.cpp builds it with
 // plain g++ under AddressSanitizer, UndefinedBehaviorSanitizer and
 // ThreadSanitizer (tests/test_host_sanitizers.py); nemo_abi.cpp is its only
 // product user.
@@ -23,6 +24,8 @@
 #include <system_error>
 #include <thread>
 #include <vector>
+
+#include "nemo_fact_kernels.h"
 
 namespace nemo {
 namespace host {
@@ -351,9 +354,7 @@ inline std::vector<double> fixed_point_colsums(int S, int E, const uint64_t* d1,
   return colsum;
 }
 
-enum FixedPointKind { kFxLog2 = 0, kFxNatural = 1 };
-
-// the bound above for a call with parent cap `cap` (0 = none; a cap >= S - 1
+// the bound above (kind: kFxLog2 or kFxNatural, nemo_fact_kernels.h) for a call with parent cap `cap` (0 = none; a cap >= S - 1
 // is no cap); cexp = the model's int8 scale exponent (Ctx::i8_cexp)
 inline double fixed_point_bound(int kind, int cexp, const std::vector<double>& colsum, int S, int E, int cap) {
   if (colsum.size() != (size_t)S + 1) return INFINITY;

@@ -17,10 +17,8 @@ constexpr int kWave = 64;
 constexpr int kMaxS = 256;         // one prep block covers all S-genes
 constexpr int kScoreWaves = 4;     // waves per score block (child split)
 constexpr int kTileCols = kWave;   // effects per score block
-constexpr int kFactWaves = 8;      // waves per factored-score block (16 effects each)
 constexpr int kI8MaxPairs = 5;     // digit-slice pairs of the int8 factored kernel
-constexpr int kWinMaxCap = 6;      // capped lookup-table kernel: parents per child
-constexpr int kWinMaxS = kMaxS;    // ... and S (LDS: ~356 S bytes per block)
+constexpr int kWinMaxS = kMaxS;    // capped lookup-table kernel's S (LDS: ~356 S bytes per block; its cap: kWinMaxCap)
 constexpr int kExactMaxSlots = 8;  // exact local optima: numpy's pairwise sum of E in <= 64 leaf blocks per part
 constexpr int kExactMaxParts = 64; // ... per numpy buffer of 8192 terms, 64 of them (E <= 524288)
 
@@ -66,10 +64,7 @@ struct Ctx {
   // factored (MFMA) path: available when every off-diagonal table row is
   // shared by all children and two-valued (all tables nem.py builds)
   int score_path = 0;              // option "score_path": 0 auto, 1 stream, 2 factored
-  int fact_kernel = 0;             // option "fact_kernel": 0 auto, 1 chunked, 2/3 f64 pipelined
-                                   // (4/8 waves), 4/5 int8 (4/5 digit pairs), 6 int8 x 8 waves,
-                                   // 7/8 int8 offset LSE (4/8 waves), 9 capped lookup tables,
-                                   // 10/11 int8 offset LSE in log2 fixed point (8/4 waves)
+  int fact_kernel = 0;             // option "fact_kernel": 0 auto, else a row of host::kFactKernels (nemo_fact_kernels.h)
   bool factored = false;
   int fspad = 0;                   // S rounded up to the MFMA row-block size
   int nwords = 0;                  // 64-bit words per D1 row
@@ -105,7 +100,7 @@ struct Ctx {
   bool i8l_ok = false;             // diagonal form and the fixed-point ranges hold
   int8_t* d_udig2 = nullptr;       // [S][8] digits of du_i / ln 2
   double* d_u0 = nullptr;          // [S] u0_i, added to G
-  // fact_kernel 20 (experiment): the prep's LDS image of each evaluation
+  // the split variant (experiment): the prep's LDS image of each evaluation
   // (G split, perm, digits) written by a prep-only launch, read by a walk-only one
   int32_t* d_i8img = nullptr;      // [i8img_cap][i8l image]
   int i8img_cap = 0;
@@ -246,7 +241,7 @@ inline hipError_t copy_sync(const Ctx& c, void* dst, const void* src, size_t byt
 // the partial buffer the score kernels write (Ctx::part_out over d_fpartial)
 inline double* fpartial(const Ctx& c) { return c.part_out ? c.part_out : c.d_fpartial; }
 
-// fact_kernel 20: bytes of one evaluation's prep image (G split [2][SPAD]
+// the split variant (FactKernel::split): bytes of one evaluation's prep image (G split [2][SPAD]
 // int, perm [SPAD] int, digits [7][SPAD][64] bytes) and its buffer for the
 // reserved batch (allocated when the option is set or the batch grows)
 inline size_t i8img_bytes(int spad) { return (size_t)spad * 460; }
@@ -319,26 +314,26 @@ hipError_t launch_refmath_probe(int fn, int n, const double* d_x, const double* 
 // number of (child, parent) pairs per chain for a given cap
 int pairs_per_chain(int S, int cap);
 
-// factored MFMA path (nemo_factored.hip)
-int factored_spad(int S);
+// factored MFMA path (nemo_factored.hip; factored_spad: nemo_fact_kernels.h)
+// partials per evaluation every partial buffer holds: the largest count of any variant
 int factored_partials(const Ctx& c);
-// the partials per evaluation the kernel fact_kernel `fk` (resolved) writes:
-// each launcher's own formula, known before anything is launched, so a
-// caller that redirects them (Ctx::part_out) checks its buffer first
+// the partials per evaluation the variant `fk` (resolved) writes: each
+// launcher's own formula, known before anything is launched, so a caller that
+// redirects them (Ctx::part_out) checks its buffer first
 int score_partials(const Ctx& c, int fk);
-// 16-effect tiles per partial of score_i8w_kernel
-constexpr int kWideSetT = 2;
 // int8 matrix-core factored path (nemo_factored_i8.hip), S <= 64, ll only:
 // one kernel (digits of Delta built in LDS + score); partials per 8-tile set
 // (*finalized: ll already written -- one block per evaluation -- else the
 // caller sums the nparts partials per evaluation with sum_partials' order)
+// k: the variant's row (family kI8: its waves and digit pairs)
 hipError_t launch_score_i8(Ctx& c, int batch, int cap, const int32_t* d_pos, const double* d_w01,
-                           double* d_ll, int np, int waves, hipStream_t st, int* nparts,
+                           double* d_ll, const host::FactKernel& k, hipStream_t st, int* nparts,
                            bool* finalized);
-// the same with the offset log-sum-exp (c.i8o_ok), waves 4 or 8 per block;
-// l2: the log2 fixed-point epilogue (c.i8l_ok)
+// the same with the offset log-sum-exp (c.i8o_ok; family kI8o) and its log2
+// fixed-point forms (c.i8l_ok; families kI8l, kI8s, kI8p): the instantiation
+// of k's waves, tiles, occupancy and split flag
 hipError_t launch_score_i8o(Ctx& c, int batch, int cap, const int32_t* d_pos, const double* d_w01,
-                            double* d_ll, int waves, bool l2, hipStream_t st, int* nparts,
+                            double* d_ll, const host::FactKernel& k, hipStream_t st, int* nparts,
                             bool* finalized);
 // the log2 kernel for 64 < S <= 128 (c.i8w_ok): one block per evaluation,
 // ll written in-kernel (*finalized)
@@ -546,8 +541,9 @@ hipError_t launch_score_factored(Ctx& c, int batch, int cap, const int32_t* d_po
 hipError_t launch_step_prep(Ctx& c, int batch, int cap, const int32_t* d_pos, const double* d_w01,
                             int32_t* d_info, hipStream_t st);
 // the fact_kernel value a factored call takes (the option, or what auto
-// resolves to for this cap / output set), with the worst-case |ll error| of
-// its fixed-point arithmetic (0 for the fp64 kernels); -1 if none applies
+// resolves to for this cap / output set: host::resolve_fact), with the
+// worst-case |ll error| of its fixed-point arithmetic (0 for the fp64
+// kernels); -1 if none applies
 int resolve_fact_kernel(const Ctx& c, int cap, bool ll_only, double* bound);
 // the step's W~ and ancestor_x from W on the device, in scipy's bits
 // (nemo_ancestor.hip; S <= 64): d_w01 = expit on the permissible entries (cap

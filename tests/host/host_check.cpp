@@ -401,6 +401,180 @@ static void check_sum_partials(std::mt19937_64& rng) {
   CHECK(sum_partials_host(small, 0) == 0.0);
 }
 
+// ---- the fact_kernel table against the decision code it replaced ---------------
+// nemo_fact_kernels.h describes the 20 factored score-kernel variants in one
+// table.  Before it, the same decisions were range tests on the option's
+// integer in resolve_fact_kernel, score_partials, factored_partials and
+// launch_score_factored, which handed launch_score_i8o a private code (0
+// register-stationary, -3 persistent, -8 eight waves at occupancy 6, -2 two
+// tiles, -20 split, else a wave count).  That code is restated here literally
+// as the specification, over the same FactModel, and the table-driven
+// functions must agree with it on every call it is defined on.
+namespace spec {
+constexpr int kFactWaves = 8, kPipeTilesPerWave = 8, kWideSetT = 2, kWinMaxCap = 6;
+
+static int factored_partials(int E) {
+  const int cols = kFactWaves * 16;
+  const int nt = (E + 15) / 16;
+  int n = ((E + cols - 1) / cols) * kFactWaves;
+  for (int wv : {4, 8}) n = std::max(n, ((nt + kPipeTilesPerWave * wv - 1) / (kPipeTilesPerWave * wv)) * wv);
+  return std::max(n, (E + 63) / 64);
+}
+
+static int score_partials(int E, int nwords, int fk) {
+  const int nt = (E + 15) / 16;
+  if (fk == 9 || fk == 15) return nwords;
+  if (fk == 18 || fk == 19) return (nt + kWideSetT - 1) / kWideSetT;
+  if (fk >= 4) return (nt + 7) / 8;
+  if (fk == 2 || fk == 3) {
+    const int wv = fk == 3 ? 8 : 4, tpb = kPipeTilesPerWave * wv;
+    return ((nt + tpb - 1) / tpb) * wv;
+  }
+  const int cols = kFactWaves * 16;
+  return ((E + cols - 1) / cols) * kFactWaves;
+}
+
+static int resolve(const FactModel& c, int option, int cap, bool ll_only, double* bound) {
+  *bound = 0.0;
+  if (cap >= c.S - 1) cap = 0;
+  const bool i8cap = c.fspad <= 64 && c.b8 && ll_only;
+  const bool wincap = ll_only && c.win_ok && cap >= 1 && cap <= kWinMaxCap;
+  auto bnd = [&](int kind) { return kind == kFxLog2 ? c.bound_log2 : c.bound_natural; };
+  const bool i8wcap = c.fspad == 128 && c.i8w_ok && c.b8 && ll_only;
+  int fk = option;
+  if (fk == 0) {
+    if (wincap) fk = 9;
+    else if (i8wcap && bnd(kFxLog2) <= c.err_budget) fk = 18;
+    else if (!i8cap) fk = 1;
+    else if (c.i8o_ok && c.i8l_ok && bnd(kFxLog2) <= c.err_budget) fk = 10;
+    else if (c.i8o_ok && bnd(kFxNatural) <= c.err_budget) fk = 8;
+    else if (!c.i8o_ok && bnd(kFxNatural) <= c.err_budget) fk = 4;
+    else fk = 2;
+  } else if (fk == 18 || fk == 19) {
+    if (!ll_only || c.fspad != 128) fk = 1;
+    else if (!i8wcap) return -1;
+  } else if (fk == 9 || fk == 15) {
+    if (!wincap) return -1;
+  } else if (fk == 2 || fk == 3) {
+    if (!(ll_only && c.fspad <= 64)) fk = 1;
+  } else if (fk >= 4) {
+    if (!i8cap) fk = 1;
+    else if ((fk == 7 || fk == 8) && !c.i8o_ok) return -1;
+    else if (fk >= 10 && !(c.i8o_ok && c.i8l_ok)) return -1;
+  }
+  const bool l2 = fk >= 10 && fk != 15, nat = fk >= 4 && fk <= 8;
+  *bound = l2 ? bnd(kFxLog2) : nat ? bnd(kFxNatural) : 0.0;
+  return fk;
+}
+
+// what launch_score_factored did with a resolved fk
+struct Launch {
+  FactFamily family;
+  int waves, tiles, occ, pairs;
+  bool round1, split, skip_prep;
+  int bound_kind;
+};
+
+static Launch launch(int fk, bool is_auto, int batch) {
+  const bool win = fk == 9 || fk == 15;
+  const bool wide = fk == 18 || fk == 19;
+  const bool l2 = fk >= 10 && fk != 15 && !wide;
+  const bool i8o = fk == 7 || fk == 8 || l2;
+  const bool i8 = fk >= 4 && fk <= 6;
+  const bool pipe = fk == 2 || fk == 3;
+  Launch L{FactFamily::kChunked, -1, -1, -1, -1, false, false, false, kFxNone};
+  L.skip_prep = !(!i8 && !i8o && !win && !wide);
+  L.bound_kind = (fk >= 10 && fk != 15) ? kFxLog2 : (fk >= 4 && fk <= 8) ? kFxNatural : kFxNone;
+  if (win) {
+    L.family = FactFamily::kWindow;
+    L.round1 = fk == 15;
+  } else if (wide) {
+    L.family = FactFamily::kI8w;
+    L.tiles = fk == 18 ? 2 : 1;
+  } else if (i8o) {
+    const int waves = fk == 20 ? -20 : fk == 17 ? -3 : fk == 13 ? 0 : fk == 14 ? -8 : fk == 16 ? 8 : fk == 12 ? 16
+                    : (fk == 7 || fk == 11) ? 4 : fk == 10 ? -2 : 8;
+    // launch_score_i8o's decoding: launch_i8s_t / launch_i8p_t, launch_i8l_t<NR, WAVES, OCC, TT, SPLIT>
+    // (defaults NEMO_I8O_WAVES_PER_SIMD, 1, false), launch_i8o_t<NR, WAVES, DIAG>
+    const int d = NEMO_I8O_WAVES_PER_SIMD, o2 = NEMO_I8L2_OCC;
+    if (l2) {
+      if (waves == 0) L.family = FactFamily::kI8s;
+      else if (waves == 16) L = Launch{FactFamily::kI8l, 16, 1, d, -1, false, false, L.skip_prep, L.bound_kind};
+      else if (waves == -3) L.family = FactFamily::kI8p;
+      else if (waves == 8) L = Launch{FactFamily::kI8l, 8, 1, d, -1, false, false, L.skip_prep, L.bound_kind};
+      else if (waves == -8) L = Launch{FactFamily::kI8l, 8, 1, 6, -1, false, false, L.skip_prep, L.bound_kind};
+      else if (waves == -2) L = Launch{FactFamily::kI8l, 8, 2, o2, -1, false, false, L.skip_prep, L.bound_kind};
+      else if (waves == -20) L = Launch{FactFamily::kI8l, 8, 2, o2, -1, false, true, L.skip_prep, L.bound_kind};
+      else L = Launch{FactFamily::kI8l, 4, 1, d, -1, false, false, L.skip_prep, L.bound_kind};
+    } else {
+      L.family = FactFamily::kI8o;
+      L.waves = waves == 8 ? 8 : 4;
+    }
+  } else if (i8) {
+    L.family = FactFamily::kI8;
+    L.waves = fk == 6 ? 8 : (fk == 4 && is_auto && batch < 384 ? 8 : 4);
+    L.pairs = fk == 5 ? 5 : 4;
+  } else if (pipe) {
+    L.family = FactFamily::kPipe;
+    L.waves = fk == 3 ? 8 : 4;
+  }
+  return L;
+}
+}  // namespace spec
+
+static void check_fact_kernels() {
+  CHECK(kFactKernelMax == 20);
+  const int sizes[] = {2, 16, 17, 64, 65, 128, 129, 256};
+  const double bounds[3][2] = {{1e-9, 1e-8}, {1e-6, 1e-8}, {1e-6, 1e-5}};  // (log2, natural) against a budget of 1e-7
+  for (int S : sizes)
+    for (int flags = 0; flags < 32; ++flags)
+      for (const auto& bd : bounds) {
+        const int E = 2000;
+        const FactModel m{S, E, nemo::factored_spad(S), (E + 63) / 64, (flags & 1) != 0, (flags & 2) != 0,
+                          (flags & 4) != 0, (flags & 8) != 0, (flags & 16) != 0, bd[0], bd[1], 1e-7};
+        for (int cap : {0, 1, 6, 7, S - 2, S - 1, S})
+          for (int ll_only = 0; ll_only < 2; ++ll_only)
+            for (int option = 0; option <= kFactKernelMax; ++option)
+              for (int batch : {1, 383, 384}) {
+                if (cap < 0) continue;
+                double sb = 0.0;
+                const int sfk = spec::resolve(m, option, cap, ll_only != 0, &sb);
+                const FactChoice ch = resolve_fact(m, option, cap, ll_only != 0, batch);
+                CHECK(ch.fk == sfk);
+                if (sfk < 0) continue;
+                const FactKernel& k = ch.k;
+                const spec::Launch L = spec::launch(sfk, option == 0, batch);
+                CHECK(k.family == L.family && k.self_prep == L.skip_prep);
+                CHECK((int)k.bound == L.bound_kind && fact_bound(k, m) == sb);
+                CHECK(k.split == L.split && k.round1 == L.round1);
+                // the fields each family's launcher reads
+                switch (k.family) {
+                  case FactFamily::kI8l: CHECK(k.waves == L.waves && k.tiles == L.tiles && k.occ == L.occ); break;
+                  case FactFamily::kI8: CHECK(k.waves == L.waves && k.pairs == L.pairs); break;
+                  case FactFamily::kI8o:
+                  case FactFamily::kPipe: CHECK(k.waves == L.waves); break;
+                  case FactFamily::kI8w: CHECK(k.tiles == L.tiles); break;
+                  case FactFamily::kChunked: CHECK(k.waves == spec::kFactWaves); break;
+                  default: break;
+                }
+              }
+      }
+  for (int E : {1, 15, 16, 17, 127, 128, 129, 2000, 8193, 524288}) {
+    const int nwords = (E + 63) / 64;
+    CHECK(fact_partials_max(E) == spec::factored_partials(E));
+    for (int fk = 1; fk <= kFactKernelMax; ++fk) {
+      CHECK(fact_partials(kFactKernels[fk], E, nwords) == spec::score_partials(E, nwords, fk));
+      CHECK(fact_partials(kFactKernels[fk], E, nwords) <= fact_partials_max(E));
+    }
+    // auto's small-batch form of 4 (8 waves) writes 4's partials
+    const FactModel m{64, E, 64, nwords, true, false, false, false, false, 1.0, 0.0, 1e-7};
+    const FactChoice ch = resolve_fact(m, 0, 0, true, 1);
+    CHECK(ch.fk == 4 && ch.k.waves == 8 && fact_partials(ch.k, E, nwords) == spec::score_partials(E, nwords, 4));
+  }
+  // only the split variant needs the prep image
+  for (int fk = 0; fk <= kFactKernelMax; ++fk) CHECK(kFactKernels[fk].split == (fk == 20));
+}
+
 int main() {
   std::mt19937_64 rng(20261017);
   check_pos_rows();
@@ -409,6 +583,7 @@ int main() {
   check_inverse_schedule(rng);
   check_step_queue(rng);
   check_sum_partials(rng);
+  check_fact_kernels();
   printf("ok %d\n", g_checks);
   return 0;
 }

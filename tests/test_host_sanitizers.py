@@ -4,8 +4,10 @@ nem-mcmc-optimization_amd/csrc/nemo_host.h holds everything libnemo.so does
 on the host without HIP: the pos checks, the staging validation (factored
 form of a table, the knockdown chains), the fixed-point error bounds, the
 InverseMethod level schedule (methods.py:117-129: levels must keep the
-sequential loop's results) and the queue behind nemo_optimal_weights_begin /
-_end.  tests/host/host_check.cpp drives all of it; here it is built with g++
+sequential loop's results), the queue behind nemo_optimal_weights_begin /
+_end and the table of factored score-kernel variants with its resolver
+(nemo_fact_kernels.h, checked against the decision code it replaced).
+tests/host/host_check.cpp drives all of it; here it is built with g++
 under AddressSanitizer + UndefinedBehaviorSanitizer and under
 ThreadSanitizer, and must run clean."""
 import os
