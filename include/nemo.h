@@ -293,10 +293,33 @@ int nemo_inverse_sweep(nemo_ctx* ctx, int nprob, const int32_t* pos, const doubl
  *                same conditions as "exact" on nemo_score, on device buffers
  *                (cells built in d_ow -- then order weights in place -- or in
  *                d_cells, not both)
- *   "exact_ok"   (get only) 1 if the staging supports "exact" (factored
- *                tables, any parent cap, E <= 524288: numpy's np.sum adds
+ *   "exact_ok"   (get only) 1 if the staging supports "exact": factored
+ *                tables, any parent cap, E <= 524288 (numpy's np.sum adds
  *                buffers of 8192 terms in order, each summed pairwise, and
- *                the local optima run one wave plan per buffer)
+ *                the local optima run one wave plan per buffer); or, with
+ *                "exact_generic", a generic table within that option's bounds
+ *   "exact_generic" 0 (default); 1 = nemo_stage_tables also stages a table
+ *                that is not factorable (real-valued rows, e.g. per-effect
+ *                log-likelihood ratios) for the exact kernels: np.exp(T) in
+ *                numpy's bits in its own [S][S][E] fp64 buffer and the wave
+ *                plan of E.  Covered ("exact_ok" 1) when E <= 8192 (one numpy
+ *                buffer) and max|T| (off-diagonal rows), max|U| <= 700; then
+ *                everything "exact" / "exact_dev" route runs the generic exact
+ *                kernels (any parent cap; the local optima read stored c rows,
+ *                "exact_form" 1 or 2 -- a form that needs the recomputed rows
+ *                runs as 2; chains x pairs x plan doubles of device memory).
+ *                Outside the bounds "exact_ok" stays 0 and the fast kernels
+ *                run.  With the option set an fp64 generic table may hold |T|
+ *                up to 705 instead of 170 (the exact kernels take no
+ *                products).  Past 170 the score calls still run on the fast
+ *                path (the streaming kernel renormalises every factor); the
+ *                other fast kernels that read exp(T) -- the fused step with
+ *                "exact" 0 or outside the bounds, nemo_score_group_dev (group
+ *                > 1), nemo_gamma_sweep, nemo_inverse_sweep -- return
+ *                NEMO_ERR_ARG on such a table.  A factorable
+ *                table takes the factored kernels whatever the option says.
+ *                Set between nemo_ctx_create and staging: on a staged context
+ *                NEMO_ERR_STATE
  *   "exact_form" the exact local-optimum kernel's form (same bits): 0 auto
  *                (default: the latency form while chains x pairs <=
  *                "exact_lat_waves", 20000 by default ~ 10 C3 chains, the slot

@@ -187,7 +187,7 @@ void nemo_ctx_destroy(nemo_ctx* ctx) {
                   c.d_udig, c.d_udig2, c.d_u0, c.d_wuw, c.d_wnull, c.d_nullsum_w, c.d_i8img,
                   c.d_xlo,  c.d_xhi,  c.d_pwplan, c.d_xcs, c.d_xcells2, c.d_xcbuf,
                   c.d_xa,   c.d_xbits, c.d_pwpos, c.d_pwmeta, c.d_xtrace, c.d_xqueue,
-                  c.d_xcost, c.d_xorder, c.d_xhist, c.d_xsbuf};
+                  c.d_xcost, c.d_xorder, c.d_xhist, c.d_xsbuf, c.d_xX};
   for (void* p : bufs)
     if (p) (void)hipFree(p);
   for (int k = 0; k < Ctx::kStepSlots; ++k) {
@@ -285,6 +285,7 @@ int alloc_tables(Ctx& c) {
   const size_t esz = c.dtype == NEMO_F64 ? 8 : 4;
   HIPCHK(hipStreamSynchronize(c.stream));
   c.staged = false;
+  c.xg_ok = false;   // (set again by the staging of a covered generic table, option exact_generic)
   void** bufs[] = {&c.d_eT, &c.d_U, (void**)&c.d_U64};
   for (void** p : bufs)
     if (*p) {
@@ -419,6 +420,43 @@ int stage_factored(nemo_ctx* ctx, bool fact, const std::vector<uint64_t>& d1,
   return NEMO_OK;
 }
 
+// option exact_generic: the exact path's tables of a generic (not factorable)
+// model, from its fp64 table still on the device: X = np.exp(T) in numpy's
+// bits in its own buffer (the fast path's exp table is untouched) and the wave
+// plan of numpy's pairwise sum of E.  Covered (c.xg_ok): E <= 8192 -- one
+// numpy buffer, the stored c rows serve one plan part -- and max|T| (the
+// off-diagonal rows, amax), max|U| <= 700, inside the SVML exp's fast path
+int stage_exact_generic(Ctx& c, const double* d_t64, double amax, const double* U) {
+  const size_t S = c.S, E = c.E;
+  c.xg_ok = false;
+  if (c.d_xX) {
+    HIPCHK(hipFree(c.d_xX));
+    c.d_xX = nullptr;
+  }
+  if (!c.exact_generic || E > 8192 || !(amax <= 700.0)) return NEMO_OK;
+  for (size_t k = 0; k < (S + 1) * E; ++k)
+    if (!(fabs(U[k]) <= 700.0)) return NEMO_OK;
+  std::vector<nemo::host::PairwisePlan> parts;
+  if (!nemo::host::build_pairwise_parts(c.E, parts) || parts.size() != 1 || parts[0].ns > nemo::kExactMaxSlots ||
+      parts[0].nh > 8)
+    return NEMO_OK;
+  std::vector<int32_t> dev, meta;
+  nemo::host::parts_device_rows(parts, dev, meta);
+  HIPCHK(dalloc(&c.d_xX, S * S * E));
+  HIPCHK(nemo::launch_exact_exp_table(c, d_t64, c.d_xX, c.stream));
+  HIPCHK(dalloc(&c.d_pwplan, dev.size()));
+  HIPCHK(dalloc(&c.d_pwmeta, meta.size()));
+  if (!c.d_xqueue) HIPCHK(dalloc(&c.d_xqueue, 1));
+  HIPCHK(nemo::copy_sync(c, c.d_pwplan, dev.data(), dev.size() * 4, hipMemcpyHostToDevice));
+  HIPCHK(nemo::copy_sync(c, c.d_pwmeta, meta.data(), meta.size() * 4, hipMemcpyHostToDevice));
+  c.pw_ns = nemo::host::parts_slots(parts);
+  c.pw_parts = 1;
+  c.pw_nh = parts[0].nh;
+  c.pw_maxrem = parts[0].maxrem;
+  c.xg_ok = true;
+  return NEMO_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -445,8 +483,20 @@ int nemo_stage_tables(nemo_ctx* ctx, const double* U, const double* T) {
         amax = std::max(amax, fabs(v));
       }
     }
-  const double lim = c.dtype == NEMO_F64 ? 170.0 : 20.0;
-  if (amax > lim)
+  // factored form: every off-diagonal row T[.][j] identical for all children
+  // and two-valued (nem.py:44-46 builds exactly that); lo_j = its first value
+  std::vector<uint64_t> d1;
+  std::vector<double> elo, ehi, tlo, thi;
+  bool fact = nemo::host::detect_factored(c.S, c.E, T, d1, elo, ehi, &tlo, &thi);
+  const bool generic = !fact;
+  // the product range: four factors of the fast kernels' products stay finite.
+  // Option exact_generic: a generic fp64 table may reach past it (a wide
+  // table, nemo_internal.h) -- the exact kernels take no products (covered to
+  // 700), score_kernel renormalises every factor of such a table, and the
+  // other fast kernels that read exp(T) refuse it (refuse_wide)
+  const double lim = c.dtype == NEMO_F64 ? nemo::kProductRangeF64 : nemo::kProductRangeF32;
+  const bool wide = amax > lim && generic && c.exact_generic && c.dtype == NEMO_F64 && amax <= nemo::kWideTableMax;
+  if (amax > lim && !wide)
     return fail(NEMO_ERR_ARG, "|T| up to %g exceeds the %s product range (%g)", amax,
                 c.dtype == NEMO_F64 ? "f64" : "f32", lim);
   for (size_t k = 0; k < (S + 1) * E; ++k)
@@ -465,19 +515,19 @@ int nemo_stage_tables(nemo_ctx* ctx, const double* U, const double* T) {
     HIPCHK(hipStreamSynchronize(c.stream));
   }
   HIPCHK(hipStreamSynchronize(c.stream));
-  HIPCHK(hipFree(d_t64));
   HIPCHK(nemo::copy_sync(c, c.d_U64, U, (S + 1) * E * 8, hipMemcpyHostToDevice));
   c.table_absmax = amax;
 
-  // factored form: every off-diagonal row T[.][j] identical for all children
-  // and two-valued (nem.py:44-46 builds exactly that); lo_j = its first value
-  std::vector<uint64_t> d1;
-  std::vector<double> elo, ehi, tlo, thi;
-  bool fact = nemo::host::detect_factored(c.S, c.E, T, d1, elo, ehi, &tlo, &thi);
   if (!fact) d1.assign((size_t)S * ((E + 63) / 64), 0ull);
   // the factored kernels' exp takes finite arguments: U must be finite too
+  // (`generic` stays: not a factorable table whose U the factored kernels cannot take)
   for (size_t k = 0; k < (S + 1) * E && fact; ++k)
     if (!isfinite(U[k]) || fabs(U[k]) > 1e9) fact = false;
+  // a generic table's exact tables (option exact_generic), while T is on the device
+  rc = generic ? stage_exact_generic(c, d_t64, amax, U) : NEMO_OK;
+  const hipError_t fe = hipFree(d_t64);
+  if (rc) return rc;
+  HIPCHK(fe);
   return stage_factored(ctx, fact, d1, elo, ehi, tlo, thi);
 }
 
@@ -540,6 +590,22 @@ static bool use_factored(const Ctx& c) {
   return c.factored;
 }
 
+// the staged model is one the exact kernels take for this call: a factored
+// model on the factored path, or a covered generic one (option exact_generic)
+static bool exact_model(const Ctx& c) {
+  return (use_factored(c) || nemo::exact_generic(c)) && nemo::exact_supported(c);
+}
+
+// a wide table (nemo_internal.h) runs the exact kernels and score_kernel only:
+// the other fast kernels' products of exp(T) are not renormalised per factor
+static int refuse_wide(const Ctx& c, const char* what) {
+  if (!nemo::wide_table(c)) return NEMO_OK;
+  return fail(NEMO_ERR_ARG,
+              "%s: |T| up to %g is past the fp64 product range (%g); such a table runs the exact kernels "
+              "(option exact_generic, |T| <= 700) and the score calls only",
+              what, c.table_absmax, nemo::kProductRangeF64);
+}
+
 // ---------------------------------------------------------------------------
 // A4+A5
 // ---------------------------------------------------------------------------
@@ -560,7 +626,7 @@ static int score_dev(nemo_ctx* ctx, int batch, const int32_t* d_pos, const doubl
   hipStream_t st = pick(ctx, stream);
   if (c.score_path == 2 && !c.factored)
     return fail(NEMO_ERR_STATE, "score_path=2 (factored) but the staged table is not factorable");
-  if (allow_exact && ctx->exact_dev && use_factored(c) && c.fact_kernel == 0 && nemo::exact_supported(c)) {
+  if (allow_exact && ctx->exact_dev && exact_model(c) && (c.fact_kernel == 0 || nemo::exact_generic(c))) {
     // nemo_score's exact path on device buffers: the cells are built in the
     // caller's d_ow (turned into order weights in place) or d_cells, else in
     // the context's scratch
@@ -599,7 +665,7 @@ int nemo_score(nemo_ctx* ctx, int batch, const int32_t* pos, const double* w01, 
   if ((rc = nemo_reserve(ctx, batch, 0))) return rc;
   const size_t S = c.S, E = c.E;
   hipStream_t st = c.stream;
-  if (use_factored(c) && c.exact && c.fact_kernel == 0 && nemo::exact_supported(c)) {
+  if (c.exact && exact_model(c) && (c.fact_kernel == 0 || nemo::exact_generic(c))) {
     // the reference's arithmetic (nemo_exact.hip) whatever the batch, so a
     // score never depends on how many orders share the call: ll and, when
     // asked, the column sums cs, the cells and the order weights
@@ -693,6 +759,7 @@ int nemo_score_group_dev(nemo_ctx* ctx, int batch, int group, const int32_t* d_p
   if (group != 1 && group != 4 && group != 8 && group != 16)
     return fail(NEMO_ERR_ARG, "group=%d not in {1,4,8,16}", group);
   if (group == 1) return nemo_score_dev(ctx, batch, d_pos, d_w01, cap, d_ll, nullptr, nullptr, nullptr, stream);
+  if ((rc = refuse_wide(c, "nemo_score_group_dev"))) return rc;
   if (batch < 0 || cap < 0) return fail(NEMO_ERR_ARG, "batch=%d cap=%d", batch, cap);
   if (batch == 0) return NEMO_OK;
   if (batch > c.cap_batch) return fail(NEMO_ERR_STATE, "batch %d > reserved %d", batch, c.cap_batch);
@@ -793,8 +860,9 @@ int nemo_local_opt(nemo_ctx* ctx, int n, const double* cvec, const double* anc, 
 namespace {
 
 // the fused step takes the reference's arithmetic for this call (option
-// exact and a factored model the exact kernels cover; any parent cap)
-bool step_exact(const Ctx& c, int) { return use_factored(c) && c.exact && nemo::exact_supported(c); }
+// exact and a model the exact kernels cover -- factored, or generic with
+// option exact_generic; any parent cap)
+bool step_exact(const Ctx& c, int) { return c.exact && exact_model(c); }
 
 // the exact fused step's buffers for nchains chains, allocated on first use
 // (never captured: step_start and nemo_optimal_weights_dev call this before
@@ -885,6 +953,7 @@ int optimal_weights_enqueue(nemo_ctx* ctx, int nchains, const int32_t* d_pos, co
     return fail(NEMO_ERR_STATE, "nchains %d > reserved %d", nchains, c.cap_chains);
   if (!step_exact(c, cap) && c.E > 80 * 64)
     return fail(NEMO_ERR_ARG, "E=%d > 5120 not supported by the fast local optima (option exact 0)", c.E);
+  if (!step_exact(c, cap) && (rc = refuse_wide(c, "the fast fused step"))) return rc;
   if (!d_pos || !d_w01 || !d_anc || !d_w_new || !d_ll1 || !d_ll_dag)
     return fail(NEMO_ERR_ARG, "null device pointer");
   hipStream_t st = pick(ctx, stream);
@@ -898,7 +967,11 @@ int optimal_weights_enqueue(nemo_ctx* ctx, int nchains, const int32_t* d_pos, co
       return fail(NEMO_ERR_STATE, "exact step buffers not reserved for %d chains", nchains);
     double* cs1 = c.d_xcs;
     double* cs2 = c.d_xcs + (size_t)nchains * c.E;
-    HIPCHK(nemo::launch_step_prep(c, nchains, cap, d_pos, d_w01, d_info, st));
+    // (a generic table: the streaming path's prep makes the same pair lists)
+    if (nemo::exact_generic(c))
+      HIPCHK(nemo::launch_prep(c, nchains, cap, d_pos, d_w01, c.d_rows, c.d_sw, c.d_cnt, c.d_pairs, st, d_info));
+    else
+      HIPCHK(nemo::launch_step_prep(c, nchains, cap, d_pos, d_w01, d_info, st));
     HIPCHK(nemo::launch_exact_eval(c, nchains, cap, d_pos, d_w01, c.d_ow, cs1, nullptr, true, st,
                                    nemo::exact_rc(c) ? c.d_xa : nullptr));
     if (anc_ready) HIPCHK(hipStreamWaitEvent(st, anc_ready, 0));  // ancestor_x from the second stream
@@ -1391,6 +1464,7 @@ int nemo_gamma_sweep(nemo_ctx* ctx, int nprob, const int32_t* pos, const double*
   if (cap < 0) return fail(NEMO_ERR_ARG, "cap=%d", cap);
   if (!w_out || !ll_out) return fail(NEMO_ERR_ARG, "null host pointer");
   Ctx& c = ctx->c;
+  if ((rc = refuse_wide(c, "nemo_gamma_sweep"))) return rc;
   const size_t S = c.S;
   hipStream_t st = c.stream;
   // opt_gamma: the evaluation takes the raw weights (methods.py:398)
@@ -1426,6 +1500,7 @@ int nemo_inverse_sweep(nemo_ctx* ctx, int nprob, const int32_t* pos, const doubl
   if (rc || nprob == 0) return rc;
   if (!w_out || !ll_out) return fail(NEMO_ERR_ARG, "null host pointer");
   Ctx& c = ctx->c;
+  if ((rc = refuse_wide(c, "nemo_inverse_sweep"))) return rc;
   const size_t S = c.S;
   hipStream_t st = c.stream;
   // levels of independent pairs that keep the reference's loop semantics
@@ -1474,6 +1549,11 @@ int nemo_set_option(nemo_ctx* ctx, const char* name, int value) {
   }
   if (strcmp(name, "exact_dev") == 0) {
     ctx->exact_dev = value ? 1 : 0;
+    return NEMO_OK;
+  }
+  if (strcmp(name, "exact_generic") == 0) {
+    if (ctx->c.staged) return fail(NEMO_ERR_STATE, "exact_generic is set before the tables are staged");
+    ctx->c.exact_generic = value ? 1 : 0;
     return NEMO_OK;
   }
   if (strcmp(name, "exact_form") == 0) {
@@ -1583,6 +1663,7 @@ int nemo_get_option(nemo_ctx* ctx, const char* name, int* value) {
   else if (strcmp(name, "graphs") == 0) *value = c.graphs;
   else if (strcmp(name, "exact") == 0) *value = c.exact;
   else if (strcmp(name, "exact_dev") == 0) *value = ctx->exact_dev;
+  else if (strcmp(name, "exact_generic") == 0) *value = c.exact_generic;
   else if (strcmp(name, "exact_form") == 0) *value = c.exact_form;
   else if (strcmp(name, "exact_cform") == 0) *value = c.exact_cform;
   else if (strcmp(name, "exact_xcd") == 0) *value = c.exact_xcd;

@@ -18,6 +18,9 @@
 // Every kernel keeps the reference's order of operations, so the bits do not
 // depend on the batch or the launch shape.  Host restatement and checks:
 // tests/host/exact_spec.cpp, tests/test_exact_spec.py; GPU: test_gpu_exact.py.
+// A real-valued (not factorable) table, option exact_generic: the cells from
+// np.exp(T) itself (exact_cells_generic_kernel) and the local optima's stored
+// c rows from its rows (setup_c's xrow); GPU: test_gpu_exact_generic.py.
 #include "lbfgsb_exact.h"
 #include "nemo_internal.h"
 #include "refmath.h"
@@ -224,6 +227,95 @@ __global__ __launch_bounds__(kCellsThreads) void exact_cells_kernel(int S, int E
       if (e < E) crow[e] = cell;
     }
   }
+}
+
+// ---------------------------------------------------------------------------
+// cells of a generic (real-valued) table, option exact_generic: every row
+// T[i][j] its own, so no factor pair serves more than one element and each
+// cell takes one SVML log per parent,
+//   cell[b][i][e] = U[i][e] + sum_j log((1.0 - s_ij) + s_ij X[i][j][e]),
+// X = np.exp(T) staged once in numpy's bits (exact_exp_table_kernel), j over
+// pi's parents of i in pi's order (the last `cap` of them), (1.0 - s) and s x
+// each rounded, then added (nem_order_mcmc.py:83-86).  Row S is U[S].  One
+// block per (evaluation, child, tile of blockDim effects), lanes over e so a
+// row of X loads coalesced; the child's parents and weights sit in LDS (one
+// broadcast read per parent), kGU parents' X loads are issued ahead of their
+// logs.  The blocks of one (child, tile) are adjacent over the evaluations and
+// an XCD takes a contiguous range of them (xcd_block, option exact_xcd), so
+// the chains of a batch read the child's X rows from one L2.
+// ---------------------------------------------------------------------------
+constexpr int kGenThreads = 256, kGenU = 4;
+
+__global__ __launch_bounds__(256) void exact_exp_table_kernel(size_t n, const double* __restrict__ t,
+                                                              double* __restrict__ x) {
+  __shared__ TabsLds tabs;
+  tabs.fill_exp(threadIdx.x, blockDim.x);
+  __syncthreads();
+  const LdsTabs tb = tabs.view();
+  for (size_t k = blockIdx.x * (size_t)blockDim.x + threadIdx.x; k < n; k += (size_t)gridDim.x * blockDim.x)
+    x[k] = refmath::svml_exp(t[k], tb);
+}
+
+__global__ __launch_bounds__(kGenThreads) void exact_cells_generic_kernel(int S, int E, int batch, int ntiles, int cap,
+                                                                          const int32_t* __restrict__ pos,
+                                                                          const double* __restrict__ w01,
+                                                                          const double* __restrict__ X,
+                                                                          const double* __restrict__ U,
+                                                                          double* __restrict__ cells, int xcd) {
+#pragma clang fp contract(off)
+  __shared__ TabsLds tabs;
+  __shared__ int perm[kMaxS];
+  __shared__ int pj[kMaxS];      // the child's parents in pi's order
+  __shared__ double ps[kMaxS];   // and their weights s_ij
+  // logical block: ((child, tile), evaluation), the evaluation fastest
+  // (xcd: option exact_xcd, as the local optima's launch)
+  const int L = xcd_block(xcd, (int)blockIdx.x, (int)gridDim.x);
+  const int b = L % batch;
+  const int it = L / batch;
+  const int tile = it % ntiles;
+  const int i = it / ntiles;   // 0 .. S
+  const int t = threadIdx.x;
+  const int e = tile * (int)blockDim.x + t;
+  const double* urow = U + (size_t)i * E;
+  double* crow = cells + ((size_t)b * (S + 1) + i) * E;
+  if (i >= S) {   // attached to nothing
+    if (e < E) crow[e] = urow[e];
+    return;
+  }
+  const int32_t* pb = pos + (size_t)b * S;
+  tabs.fill_log(t, blockDim.x);
+  for (int q = t; q < S; q += blockDim.x) perm[pb[q]] = q;
+  __syncthreads();
+  const int p0 = pb[i];
+  const int lo = (cap > 0 && p0 > cap) ? p0 - cap : 0;
+  const int np = p0 - lo;
+  for (int q = t; q < np; q += blockDim.x) {
+    const int j = perm[lo + q];
+    pj[q] = j;
+    ps[q] = w01[((size_t)b * S + i) * S + j];
+  }
+  __syncthreads();
+  if (e >= E) return;
+  const LdsTabs tb = tabs.view();
+  const double* xi = X + (size_t)i * S * E + e;
+  double cell = urow[e];
+  int q = 0;
+  for (; q + kGenU <= np; q += kGenU) {
+    double x[kGenU], s[kGenU];
+#pragma unroll
+    for (int u = 0; u < kGenU; ++u) {
+      x[u] = xi[(size_t)__builtin_amdgcn_readfirstlane(pj[q + u]) * E];
+      s[u] = ps[q + u];
+    }
+#pragma unroll
+    for (int u = 0; u < kGenU; ++u) cell = cell + refmath::svml_log((1.0 - s[u]) + s[u] * x[u], tb);
+  }
+  for (; q < np; ++q) {
+    const double x = xi[(size_t)__builtin_amdgcn_readfirstlane(pj[q]) * E];
+    const double s = ps[q];
+    cell = cell + refmath::svml_log((1.0 - s) + s * x, tb);
+  }
+  crow[e] = cell;
 }
 
 // ---------------------------------------------------------------------------
@@ -719,6 +811,9 @@ struct CArgs {
   size_t pd = 0;
   // kSlot (form 7): one plan-ordered c row set per resident wave, [waves][pd]
   double* sbuf = nullptr;
+  // a generic table (option exact_generic): X = np.exp(T) [S][S][E]; the
+  // stored rows take lv = X[i][k][e] in place of the two-valued lookup
+  const double* xg = nullptr;
 };
 
 // The persistent form (option exact_persist): resident blocks whose waves take
@@ -735,7 +830,8 @@ __device__ __forceinline__ int next_item(int* q, int lane) {
 template <class Obj, int NS, bool kRc>
 __device__ __forceinline__ void setup_c(Obj& obj, const CArgs& ca, int S, int E, int b, int k, size_t gw, double s,
                                         double lvlo, double lvhi, const double* __restrict__ owk,
-                                        const uint64_t* __restrict__ d1w, int nwords, int lane, unsigned slots) {
+                                        const uint64_t* __restrict__ d1w, int nwords, int lane, unsigned slots,
+                                        const double* __restrict__ xrow = nullptr) {
 #pragma clang fp contract(off)
   constexpr size_t kPlanD = (size_t)NS * Obj::kRows * kWave;   // (one part: the stored form)
   if (kRc) {
@@ -751,7 +847,8 @@ __device__ __forceinline__ void setup_c(Obj& obj, const CArgs& ca, int S, int E,
   }
   auto cval = [&](int e) {
 #pragma clang fp contract(off)
-    const double lv = d1bit(d1w, nwords, k, e) ? lvhi : lvlo;
+    // (xrow: a generic table's np.exp(T[i][k]), uniform over the wave)
+    const double lv = xrow ? xrow[e] : d1bit(d1w, nwords, k, e) ? lvhi : lvlo;
     const double a = (lv - 1.0) * owk[e];
     const double bd = (1.0 - s * a) + s * (lv - 1.0);
     return a / bd;
@@ -870,7 +967,8 @@ __attribute__((amdgpu_waves_per_eu(kSlot ? NEMO_EXACT_SLOT_WAVES : kCt ? NEMO_EX
     setup_slot<Obj, NS>(obj, ca, S, b, k, s, xlo[k], xhi[k], lane,
                         ca.sbuf + ((size_t)blockIdx.x * kExactWaves + wv) * ca.pd);
   else
-    setup_c<Obj, NS, kRc>(obj, ca, S, E, b, k, (size_t)gw, s, xlo[k], xhi[k], owk, d1w, nwords, lane, ~0u);
+    setup_c<Obj, NS, kRc>(obj, ca, S, E, b, k, (size_t)gw, s, ca.xg ? 0.0 : xlo[k], ca.xg ? 0.0 : xhi[k], owk, d1w,
+                          nwords, lane, ~0u, ca.xg ? ca.xg + ((size_t)i * S + k) * E : nullptr);
   obj.nparts = ca.nparts;
   obj.plg = ca.plan;
   obj.pmeta = ca.pmeta;
@@ -981,8 +1079,9 @@ __global__ __launch_bounds__(2 * kWave) __attribute__((amdgpu_waves_per_eu(4, 4)
   obj.half = wv;
   obj.load_plan();
   // this wave's slots' rows (it alone reads them)
-  setup_c<Obj, NS, kRc>(obj, ca, S, E, b, k, (size_t)gw, s, xlo[k], xhi[k], owk, d1w, nwords, lane,
-                        wv ? 0xaaaaaaaau : 0x55555555u);
+  setup_c<Obj, NS, kRc>(obj, ca, S, E, b, k, (size_t)gw, s, ca.xg ? 0.0 : xlo[k], ca.xg ? 0.0 : xhi[k], owk, d1w,
+                        nwords, lane, wv ? 0xaaaaaaaau : 0x55555555u,
+                        ca.xg ? ca.xg + ((size_t)i * S + k) * E : nullptr);
   LbxState& st = *reinterpret_cast<LbxState*>(lst_raw[wv]);
   lbx_init(st, s);
   long long c_obj = 0, c_ctl = 0, tc = ca.trace ? (long long)clock64() : 0;   // (trace: shader cycles)
@@ -1431,7 +1530,17 @@ hipError_t launch_refmath_probe(int fn, int n, const double* d_x, const double* 
   return hipGetLastError();
 }
 
-bool exact_supported(const Ctx& c) { return c.factored && c.exact_ok && c.d_xlo && c.d_pwplan; }
+bool exact_supported(const Ctx& c) {
+  if (exact_generic(c)) return c.d_xX && c.d_pwplan;
+  return c.factored && c.exact_ok && c.d_xlo && c.d_pwplan;
+}
+
+hipError_t launch_exact_exp_table(Ctx& c, const double* d_T64, double* d_X, hipStream_t st) {
+  const size_t n = (size_t)c.S * c.S * c.E;
+  const int blocks = (int)std::min<size_t>((n + 255) / 256, 8192);
+  exact_exp_table_kernel<<<blocks, 256, 0, st>>>(n, d_T64, d_X);
+  return hipGetLastError();
+}
 
 size_t exact_plan_doubles(const Ctx& c) {
   return (size_t)c.pw_parts * c.pw_ns * (ExactObjective<1, true, true>::kRows * kWave);
@@ -1440,14 +1549,25 @@ size_t exact_plan_doubles(const Ctx& c) {
 hipError_t launch_exact_eval(Ctx& c, int batch, int cap, const int32_t* d_pos, const double* d_w01, double* d_cells,
                              double* d_cs, double* d_ll, bool want_ow, hipStream_t st, double* d_xa) {
   const int S = c.S, E = c.E;
-  // one wave per group of 4 D1 words, at most kCellsThreads / 64 waves; 8
-  // children per block once the batch alone fills the chip
-  const int cw = std::min(kCellsThreads / kWave, std::max(1, (c.nwords + 3) / 4));
-  const int rows = batch >= 512 ? std::min(kCellsRows, kCellsSlots / S) : 1;
-  const int nchunk = (S + rows) / rows;
-  exact_cells_kernel<<<dim3(batch * nchunk), cw * kWave, 0, st>>>(S, E, rows, cap >= S - 1 ? 0 : cap, d_pos, d_w01,
-                                                                  c.d_xlo, c.d_xhi,
-                                                                  c.d_D1w, c.nwords, c.d_U64, d_cells);
+  if (exact_generic(c)) {
+    // a generic table: one block per (child, tile of effects, evaluation)
+    const int threads = std::min(kGenThreads, ((E + kWave - 1) / kWave) * kWave);
+    const int ntiles = (E + threads - 1) / threads;
+    const size_t nblk = (size_t)(S + 1) * ntiles * batch;
+    if (nblk > 0x7fffffffu) return hipErrorInvalidValue;
+    exact_cells_generic_kernel<<<dim3((unsigned)nblk), threads, 0, st>>>(S, E, batch, ntiles, cap >= S - 1 ? 0 : cap,
+                                                                         d_pos, d_w01, c.d_xX, c.d_U64, d_cells,
+                                                                         c.exact_xcd);
+  } else {
+    // one wave per group of 4 D1 words, at most kCellsThreads / 64 waves; 8
+    // children per block once the batch alone fills the chip
+    const int cw = std::min(kCellsThreads / kWave, std::max(1, (c.nwords + 3) / 4));
+    const int rows = batch >= 512 ? std::min(kCellsRows, kCellsSlots / S) : 1;
+    const int nchunk = (S + rows) / rows;
+    exact_cells_kernel<<<dim3(batch * nchunk), cw * kWave, 0, st>>>(S, E, rows, cap >= S - 1 ? 0 : cap, d_pos, d_w01,
+                                                                    c.d_xlo, c.d_xhi, c.d_D1w, c.nwords, c.d_U64,
+                                                                    d_cells);
+  }
   hipError_t err = hipGetLastError();
   if (err != hipSuccess) return err;
   const size_t nthr = (size_t)batch * E;
@@ -1668,6 +1788,7 @@ hipError_t launch_local_opt_exact(Ctx& c, int nchains, int npairs, const int32_t
   a.ca.pmeta = c.d_pwmeta;
   a.ca.pd = exact_plan_doubles(c);
   a.ca.sbuf = c.d_xsbuf;
+  a.ca.xg = exact_generic(c) ? c.d_xX : nullptr;   // (stored rows: exact_rc is false for a generic table)
   c.xtrace_n = a.ca.trace ? nw : 0;
   switch (c.pw_ns) {
     case 1: launch_lo_ns<1>(a, form, rc, grid, st); break;

@@ -165,6 +165,14 @@ struct Ctx {
   long long* d_xtrace = nullptr;
   size_t cap_xtrace = 0;           // its optima
   int xtrace_n = 0;                // optima the last traced launch recorded
+  // option "exact_generic" (0 default; set before staging): nemo_stage_tables
+  // also stages a generic (not factorable) table for the exact kernels -- X =
+  // np.exp(T) in numpy's bits and the wave plan of E -- when E <= 8192 (one
+  // numpy buffer: the stored c rows serve one plan part) and max|T|, max|U| <=
+  // 700 (inside the SVML exp's fast path)
+  int exact_generic = 0;
+  bool xg_ok = false;              // the staged generic table is covered
+  double* d_xX = nullptr;          // [S][S][E] numpy's exp(T) (refmath::svml_exp)
 
   // worst-case |ll error| of the fixed-point kernels (nemo_host.h):
   // fx_colsum[k] = sum_e min(colbits_e, k) over the staged D1 bits; auto takes
@@ -290,7 +298,18 @@ size_t exact_plan_doubles(const Ctx& c);   // one plan-ordered row set (per opti
 size_t exact_slot_doubles(const Ctx& c);   // the slot form's row sets: its resident waves x one row set
 // the local optima recompute c from the parents' a rows (option exact_cform 1,
 // and always for a plan in two parts, which the stored rows do not serve)
-inline bool exact_rc(const Ctx& c) { return c.exact_cform == 1 || c.pw_parts > 1; }
+// A wide table: staged past the fp64 product range (|T| <= 170, where four
+// factors of the fast kernels' products stay finite) -- only a generic fp64
+// table with option exact_generic, up to kWideTableMax.  The exact kernels
+// take no products and score_kernel renormalises every factor of such a
+// table; every other fast kernel that reads exp(T) refuses it (nemo_abi.cpp)
+constexpr double kProductRangeF64 = 170.0, kProductRangeF32 = 20.0, kWideTableMax = 705.0;
+inline bool wide_table(const Ctx& c) { return c.dtype == 0 && c.table_absmax > kProductRangeF64; }
+// (a generic table has no a rows to recompute from: always the stored form)
+inline bool exact_generic(const Ctx& c) { return !c.factored && c.xg_ok; }
+inline bool exact_rc(const Ctx& c) { return !exact_generic(c) && (c.exact_cform == 1 || c.pw_parts > 1); }
+// X = np.exp(T) of a generic table in numpy's bits, [S][S][E] from the fp64 host layout
+hipError_t launch_exact_exp_table(Ctx& c, const double* d_T64, double* d_X, hipStream_t st);
 // eval in the reference's order: cells into d_cells [batch][S+1][E] (with
 // want_ow: replaced by the order weights), cs into d_cs [batch][E], ll into
 // d_ll (nullable: left to the caller)

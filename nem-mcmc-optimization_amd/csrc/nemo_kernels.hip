@@ -114,7 +114,11 @@ __global__ __launch_bounds__(256) void prep_kernel(int S, int cap, const int32_t
 // score: one evaluation x 64 effects per block, children split over waves.
 // grid = ntiles * batch (1-D, XCD-remapped), block = kScoreWaves * 64.
 // ---------------------------------------------------------------------------
-template <typename TT, bool RENORM>
+// RENORM: 0 the product as it is; 1 renormalised after every 4th factor (4
+// factors stay finite while |T| <= 170: the staging's product range); 2 after
+// every factor (a wide generic table, option exact_generic: |T| <= 705, so a
+// factor and a renormalised product times a factor stay normal doubles)
+template <typename TT, int RENORM>
 __global__ __launch_bounds__(kScoreWaves * kWave) void score_kernel(
     int S, int E, int ntiles, const TT* __restrict__ eT, const TT* __restrict__ U,
     const int32_t* __restrict__ rows, const double* __restrict__ sw,
@@ -159,7 +163,7 @@ __global__ __launch_bounds__(kScoreWaves * kWave) void score_kernel(
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
         prod *= A::term((PT)ss[k], vv[k]);
-        if (RENORM && (k & 3) == 3) prod = A::renorm(prod, expo);
+        if (RENORM == 2 || (RENORM && (k & 3) == 3)) prod = A::renorm(prod, expo);
       }
     }
     for (; t < n; ++t) {
@@ -828,9 +832,11 @@ hipError_t launch_score(Ctx& c, int batch, const int32_t* d_rows, const double* 
       c.S, c.E, nt, (const TT*)c.d_eT, (const TT*)c.d_U, d_rows, d_sw, d_cnt, c.d_partial,   \
       d_cs, d_cells, d_ow, c.xcd_remap)
   if (c.dtype == 0) {
-    if (rn) NEMO_SC(double, true); else NEMO_SC(double, false);
+    if (wide_table(c)) NEMO_SC(double, 2);
+    else if (rn) NEMO_SC(double, 1);
+    else NEMO_SC(double, 0);
   } else {
-    if (rn) NEMO_SC(float, true); else NEMO_SC(float, false);
+    if (rn) NEMO_SC(float, 1); else NEMO_SC(float, 0);
   }
 #undef NEMO_SC
   hipError_t err = hipGetLastError();

@@ -7,9 +7,9 @@ local optimisation run as hand-written HIP kernels for gfx950 behind the C-ABI
 of ``include/nemo.h`` (``libnemo.so``, loaded with ctypes).
 """
 from . import generator, utils
-from .nem import NEM
+from .nem import NEM, TableModel
 
-__all__ = ["NEM", "generator", "utils", "Engine", "NEMOrderMCMC", "ExactArithmeticWarning"]
+__all__ = ["NEM", "TableModel", "generator", "utils", "Engine", "NEMOrderMCMC", "ExactArithmeticWarning"]
 
 
 def __getattr__(name):

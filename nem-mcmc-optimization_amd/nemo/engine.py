@@ -31,9 +31,14 @@ class Engine:
     score tables (nem.py:49-64).  ``dtype='f32'`` stores exp(T) and U in fp32
     and runs the per-element products in fp32 (the C5 configuration); logs,
     log-sum-exp and the effect sum stay fp64.
+
+    ``exact_generic=True`` (option ``exact_generic``, set before staging):
+    real-valued tables that are not factorable are staged for the
+    reference-arithmetic kernels too -- covered for E <= 8192 and max|T|,
+    max|U| <= 700 (``exact_status``); a factorable table is unaffected.
     """
 
-    def __init__(self, U, T, device: int = 0, dtype: str = "f64"):
+    def __init__(self, U, T, device: int = 0, dtype: str = "f64", exact_generic: bool = False):
         U = f64(U)
         T = f64(T)
         if T.ndim != 3 or T.shape[0] != T.shape[1]:
@@ -42,6 +47,8 @@ class Engine:
         if U.shape != (S + 1, E):
             raise ValueError(f"U must be ({S + 1}, {E}), got {U.shape}")
         self._create(S, E, device, dtype)
+        if exact_generic:
+            self.set_option("exact_generic", 1)
         check(_lib.load().nemo_stage_tables(self._ctx, ptr(U), ptr(T)))
 
     def _create(self, S, E, device, dtype):
@@ -73,7 +80,11 @@ class Engine:
     @classmethod
     def for_nem(cls, nem, device: int = 0, dtype: str = "f64") -> "Engine":
         """The model's engine (one per device and dtype), staged from its
-        knockdown matrix on the GPU (``from_knockdown``)."""
+        knockdown matrix on the GPU (``from_knockdown``).  A model that holds
+        tables and no knockdown matrix (``nemo.nem.TableModel``) is staged
+        from its tables (``for_model``)."""
+        if getattr(nem, "observed_knockdown_mat", None) is None:
+            return cls.for_model(nem, device=device, dtype=dtype)
         cache = nem.__dict__.setdefault("_nemo_engines", {})
         key = (device, dtype)
         eng = cache.get(key)
@@ -84,16 +95,33 @@ class Engine:
         return eng
 
     @classmethod
-    def for_tables(cls, U, score_tables, device: int = 0, dtype: str = "f64") -> "Engine":
+    def for_model(cls, model, device: int = 0, dtype: str = "f64", exact_generic: bool = True) -> "Engine":
+        """The engine of a table model (``nemo.nem.TableModel``: ``U`` and
+        ``get_score_tables``), one per device, dtype and ``exact_generic``,
+        cached on the model as ``for_nem`` caches a NEM's."""
+        cache = model.__dict__.setdefault("_nemo_engines", {})
+        key = (device, dtype, bool(exact_generic))
+        eng = cache.get(key)
+        if eng is None:
+            t = np.asarray(model.get_score_tables(None), dtype=np.float64)
+            eng = cls(model.U, t, device=device, dtype=dtype, exact_generic=exact_generic)
+            cache[key] = eng
+        return eng
+
+    @classmethod
+    def for_tables(cls, U, score_tables, device: int = 0, dtype: str = "f64",
+                   exact_generic: bool = False) -> "Engine":
         """Engine for the (U, score_tables) pair a caller of methods.py holds:
         the model's cached engine, staged from D, when the tables are a NEM's
-        lazy tables and U is its U; else a new engine on the given tables."""
+        lazy tables and U is its U; else a new engine on the given tables
+        (``exact_generic``: as ``Engine``)."""
         from .nem import ScoreTables
         if isinstance(score_tables, ScoreTables):
             nem = score_tables._nem
             if score_tables.knockdown_mat is nem.observed_knockdown_mat and np.array_equal(U, nem.U):
                 return cls.for_nem(nem, device=device, dtype=dtype)
-        return cls(U, np.asarray(score_tables, dtype=np.float64), device=device, dtype=dtype)
+        return cls(U, np.asarray(score_tables, dtype=np.float64), device=device, dtype=dtype,
+                   exact_generic=exact_generic)
 
     @property
     def handle(self):
@@ -275,7 +303,8 @@ class Engine:
         covered and what the sampler does outside it)."""
         from .limits import exact_limits
         return exact_limits(self.S, self.E, self.factored, cap, host_blas_arch(),
-                            exact_option=bool(self.get_option("exact")))
+                            exact_option=bool(self.get_option("exact")),
+                            exact_generic=bool(self.get_option("exact_generic")))
 
     def exact_status(self, cap: int = 0):
         """(True, "") when the fused step and the sampler's score calls run in
@@ -286,6 +315,9 @@ class Engine:
         ok, why = exact_status_from(self.exact_limits(cap))
         # the library's own verdict on the staging (the wave plan it built)
         if ok and not self.get_option("exact_ok"):
+            if not self.factored:
+                return False, ("table form: the staged generic table is outside option exact_generic's bounds "
+                               "(max|T| and max|U| <= 700); the fast kernels")
             return False, f"E={self.E}: the staging found no wave plan for numpy's pairwise sum; the fast kernels"
         return ok, why
 

@@ -27,6 +27,11 @@ MAX_E_FAST_LOCAL_OPT = 80 * 64
 
 NUMPY_BUFSIZE = 8192      # np.getbufsize(): np.sum adds buffer-sized chunks in order
 MAX_PARTS = 64            # csrc/nemo_internal.h kExactMaxParts
+# option exact_generic (csrc/nemo_abi.cpp stage_exact_generic): one numpy
+# buffer -- the stored c rows serve one wave plan -- and tables inside the
+# SVML exp's fast path
+MAX_E_EXACT_GENERIC = NUMPY_BUFSIZE
+MAX_ABS_EXACT_GENERIC = 700.0
 
 
 def pairwise_parts(E: int):
@@ -69,17 +74,31 @@ class Limit:
 
 
 def exact_limits(S: int, E: int, factored: bool, cap: int = 0, host_blas: str | None = "SkylakeX",
-                 exact_option: bool = True) -> list[Limit]:
-    """The exact path's limits for a model of S S-genes and E effects."""
+                 exact_option: bool = True, *, exact_generic: bool = False) -> list[Limit]:
+    """The exact path's limits for a model of S S-genes and E effects.
+    ``exact_generic``: the engine's option of that name (set before staging)
+    -- a generic, real-valued table is covered too within its bounds."""
     leaves = pairwise_leaves(E)
     parts = pairwise_parts(E)
+    if exact_generic:
+        table_form = Limit(
+            "table form", "factored: every off-diagonal row T[.][j] shared by all children, two-valued (every "
+            f"table nem.py builds); or, with option exact_generic, any real-valued table with E <= "
+            f"{MAX_E_EXACT_GENERIC} (one numpy buffer) and max|T|, max|U| <= {MAX_ABS_EXACT_GENERIC:g}",
+            "factored" if factored else f"generic, E={E}", bool(factored) or E <= MAX_E_EXACT_GENERIC,
+            f"ExactArithmeticWarning (strict=True: RuntimeError); the fast kernels -- a generic table with E > "
+            f"{MAX_E_EXACT_GENERIC} or max|T|, max|U| > {MAX_ABS_EXACT_GENERIC:g} (Engine.exact_status reads the "
+            "library's verdict on the staged values)", False)
+    else:
+        table_form = Limit(
+            "table form", "factored: every off-diagonal row T[.][j] shared by all children, two-valued "
+            "(every table nem.py builds)", "factored" if factored else "generic", bool(factored),
+            "ExactArithmeticWarning (strict=True: RuntimeError); the fast kernels", False)
     rows = [
         Limit("option exact", "1 (default)", "1" if exact_option else "0", bool(exact_option),
               "the fast kernels: scores within ~1e-9, a local optimum may take another line-search path",
               False),
-        Limit("table form", "factored: every off-diagonal row T[.][j] shared by all children, two-valued "
-              "(every table nem.py builds)", "factored" if factored else "generic", bool(factored),
-              "ExactArithmeticWarning (strict=True: RuntimeError); the fast kernels", False),
+        table_form,
         Limit("E (effects)", f"np.sum of E terms in <= {MAX_PARTS} numpy buffers of {NUMPY_BUFSIZE} (E <= "
               f"{MAX_PARTS * NUMPY_BUFSIZE}; each buffer summed pairwise in <= {MAX_LEAVES} leaf blocks, the "
               "buffers in order) -- with numpy's default np.getbufsize()",

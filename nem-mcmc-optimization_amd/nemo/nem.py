@@ -69,6 +69,52 @@ class ScoreTables:
         return self._d
 
 
+class TableModel:
+    """A model given by its tables: ``U`` (S+1, E) and ``T`` (S, S, E), real
+    valued.  ``NEMOrderMCMC``, ``ChainBatch`` and the replica driver take it in
+    place of a ``NEM``: it has the attributes they read (``num_s``, ``num_e``,
+    ``U``, ``get_score_tables``) and no knockdown matrix, so its engine is
+    staged from the tables (``Engine.for_model``, option ``exact_generic``:
+    the reference's bits for E <= 8192 and max|T|, max|U| <= 700).
+
+    A sampler built on a ``TableModel`` without an ``engine=`` always takes
+    that option, and with it the exact step's stored rows (chains x pairs x
+    plan doubles of device memory: 0.56 GB at 64 x 2000, 16 chains).  To run
+    the model without it, stage ``Engine(U, T)`` yourself and pass it as
+    ``engine=``."""
+
+    observed_knockdown_mat = None
+
+    def __init__(self, U, T):
+        T = np.ascontiguousarray(T, dtype=np.float64)
+        U = np.ascontiguousarray(U, dtype=np.float64)
+        if T.ndim != 3 or T.shape[0] != T.shape[1]:
+            raise ValueError(f"T must be (S, S, E), got {T.shape}")
+        if U.shape != (T.shape[0] + 1, T.shape[2]):
+            raise ValueError(f"U must be ({T.shape[0] + 1}, {T.shape[2]}), got {U.shape}")
+        self.num_s, self.num_e = int(T.shape[0]), int(T.shape[2])
+        self.U, self.T = U, T
+
+    @classmethod
+    def from_log_ratios(cls, R) -> "TableModel":
+        """The model of per-effect log-likelihood ratios R (S, E), R[j][e] =
+        l1 - l0 of effect e under the knockdown of S-gene j: nem.py:25-64 with
+        the two-valued increments replaced by R and the per-effect constant
+        sum_j l0 dropped -- every child shares parent j's row, T[i][j] = R[j]
+        (the diagonal row T[i][i] = R[i] is U's row i), and U = [R; 0]."""
+        R = np.ascontiguousarray(R, dtype=np.float64)
+        if R.ndim != 2:
+            raise ValueError(f"R must be (S, E), got {R.shape}")
+        s, e = R.shape
+        T = np.empty((s, s, e), dtype=np.float64)
+        T[:] = R[None, :, :]
+        return cls(np.vstack([R, np.zeros((1, e))]), T)
+
+    def get_score_tables(self, _knockdown_mat=None):
+        """The tables themselves (the same array on every call)."""
+        return self.T
+
+
 class NEM:
     """Reference: nem.py:8-22.
 

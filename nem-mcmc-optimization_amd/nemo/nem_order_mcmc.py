@@ -94,7 +94,10 @@ class NEMOrderMCMC:
         0 = every predecessor, as in the reference), ``engine`` (share a staged
         model between samplers), ``strict`` (raise instead of warning when the
         staged model is outside the reference-arithmetic kernels; an engine
-        whose option ``exact`` was set to 0 on purpose is not checked)."""
+        whose option ``exact`` was set to 0 on purpose is not checked).
+        ``nem`` may be a ``nemo.nem.TableModel`` (real-valued tables): without
+        ``engine`` it is staged with option ``exact_generic`` set
+        (``Engine.for_model``); pass an engine of your own to opt out."""
         self.nem = nem
         self.num_s = nem.num_s
         self.num_e = nem.num_e
