@@ -93,6 +93,16 @@ int nemo_stage_tables(nemo_ctx* ctx, const double* U, const double* T);
  * Stages bit-for-bit what nemo_stage_tables stages for those U and T, with
  * no S*S*E host table (655 MB at C5 in fp64). */
 int nemo_stage_knockdown(nemo_ctx* ctx, const uint8_t* D, double A, double B);
+/* the model of per-effect log-likelihood ratios R [S][E]
+ * (TableModel.from_log_ratios): T[i][j] = R[j] for every child i and parent j,
+ * U [S+1][E] as given.  R alone crosses to the device, where the table is
+ * made by a broadcast; from there on it is nemo_stage_tables' own path, so
+ * everything obtainable afterwards equals, to the bit, what
+ * nemo_stage_tables(U, T) with that T gives under the same options -- with no
+ * S*S*E host table (65 MB at 64 x 2000, 655 MB at 128 x 5000).  A two-valued R
+ * stages the factored kernels; a real-valued one with "exact_generic" is a
+ * row-shared table ("exact_shared"). */
+int nemo_stage_log_ratios(nemo_ctx* ctx, const double* U, const double* R);
 
 /* ---- A4+A5: batched order-score evaluation --------------------------------
  * Replaces NEMOrderMCMC.compute_cell_ratios + calculate_ll
@@ -301,13 +311,24 @@ int nemo_inverse_sweep(nemo_ctx* ctx, int nprob, const int32_t* pos, const doubl
  *   "exact_generic" 0 (default); 1 = nemo_stage_tables also stages a table
  *                that is not factorable (real-valued rows, e.g. per-effect
  *                log-likelihood ratios) for the exact kernels: np.exp(T) in
- *                numpy's bits in its own [S][S][E] fp64 buffer and the wave
- *                plan of E.  Covered ("exact_ok" 1) when E <= 8192 (one numpy
- *                buffer) and max|T| (off-diagonal rows), max|U| <= 700; then
- *                everything "exact" / "exact_dev" route runs the generic exact
- *                kernels (any parent cap; the local optima read stored c rows,
- *                "exact_form" 1 or 2 -- a form that needs the recomputed rows
- *                runs as 2; chains x pairs x plan doubles of device memory).
+ *                numpy's bits in its own fp64 buffer and the wave plan of E.
+ *                Covered ("exact_ok" 1) when max|T| (off-diagonal rows), max|U|
+ *                <= 700 and
+ *                  - a table with its own rows per child: E <= 8192 (one numpy
+ *                    buffer); X is [S][S][E] and the local optima read stored
+ *                    c rows ("exact_form" 1 or 2 -- a form that needs the
+ *                    recomputed rows runs as 2; chains x pairs x plan doubles
+ *                    of device memory);
+ *                  - a row-shared table (T[i][j] bit-identical for every child
+ *                    i != j; what nemo_stage_log_ratios stages): E <= 524288 as
+ *                    for factored tables; X is [S][E], and the local optima
+ *                    follow "exact_cform" like the factored model -- per
+ *                    (chain, parent) recompute rows, chains x S x plan doubles,
+ *                    with lv - 1 a real number per element in place of the two
+ *                    values a bit selects ("exact_form" 1, 2, 4 and 7; 3 and 5
+ *                    run as 2).
+ *                Then everything "exact" / "exact_dev" route runs the generic
+ *                exact kernels (any parent cap).
  *                Outside the bounds "exact_ok" stays 0 and the fast kernels
  *                run.  With the option set an fp64 generic table may hold |T|
  *                up to 705 instead of 170 (the exact kernels take no
@@ -335,7 +356,18 @@ int nemo_inverse_sweep(nemo_ctx* ctx, int nprob, const int32_t* pos, const doubl
  *                the resident wave's own row set in device memory, read at
  *                each evaluation; needs "exact_cform" 1 and "exact_persist",
  *                else the throughput form); E > 8192 always runs the
- *                throughput form
+ *                throughput form.  A row-shared real-valued table
+ *                ("exact_shared") with recompute rows has forms 1, 2, 4 and 7;
+ *                the pair and dual forms run as 2 there, and auto changes to
+ *                the slot form at a quarter of "exact_lat_waves" (measured
+ *                ahead from 4 chains at 64 x 2000)
+ *   "exact_shared" (get only) 1 if the staged generic table is row-shared
+ *   "exact_rc"   (get only) 1 if the exact local optima recompute c from the
+ *                per-parent a rows, 0 if they read stored c rows
+ *   "exact_form_used" (get only) the form the last exact local-optimum launch
+ *                ran after every fall-back (1 latency, 2 throughput, 3 pair, 4
+ *                cached throughput, 5 dual, 6 the throughput form over several
+ *                plan parts, 7 slot); 0 before any launch
  *   "timing_kernel" 0 (default): nemo_timing_enable / _read time the score
  *                kernels; 1: the exact local optima's kernel (bench.py)
  *   "anc_overlap" 1 (default): nemo_optimal_weights_w makes ancestor_x on a

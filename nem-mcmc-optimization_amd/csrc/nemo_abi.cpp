@@ -187,7 +187,7 @@ void nemo_ctx_destroy(nemo_ctx* ctx) {
                   c.d_udig, c.d_udig2, c.d_u0, c.d_wuw, c.d_wnull, c.d_nullsum_w, c.d_i8img,
                   c.d_xlo,  c.d_xhi,  c.d_pwplan, c.d_xcs, c.d_xcells2, c.d_xcbuf,
                   c.d_xa,   c.d_xbits, c.d_pwpos, c.d_pwmeta, c.d_xtrace, c.d_xqueue,
-                  c.d_xcost, c.d_xorder, c.d_xhist, c.d_xsbuf, c.d_xX};
+                  c.d_xcost, c.d_xorder, c.d_xhist, c.d_xsbuf, c.d_xX, c.d_xl};
   for (void* p : bufs)
     if (p) (void)hipFree(p);
   for (int k = 0; k < Ctx::kStepSlots; ++k) {
@@ -423,34 +423,62 @@ int stage_factored(nemo_ctx* ctx, bool fact, const std::vector<uint64_t>& d1,
 // option exact_generic: the exact path's tables of a generic (not factorable)
 // model, from its fp64 table still on the device: X = np.exp(T) in numpy's
 // bits in its own buffer (the fast path's exp table is untouched) and the wave
-// plan of numpy's pairwise sum of E.  Covered (c.xg_ok): E <= 8192 -- one
-// numpy buffer, the stored c rows serve one plan part -- and max|T| (the
-// off-diagonal rows, amax), max|U| <= 700, inside the SVML exp's fast path
-int stage_exact_generic(Ctx& c, const double* d_t64, double amax, const double* U) {
+// plan of numpy's pairwise sum of E.  Covered (c.xg_ok): max|T| (the
+// off-diagonal rows, amax), max|U| <= 700, inside the SVML exp's fast path, and
+//   * a table with its own rows per child: E <= 8192 -- one numpy buffer, the
+//     stored c rows serve one plan part;
+//   * a row-shared table (`shared`, host::detect_row_shared): E within the
+//     factored model's plans (kExactMaxParts parts of kExactMaxSlots slots).
+//     X holds one row per parent, [S][E]; the recompute rows' lv - 1 in plan
+//     order (d_xl) and the element -> plan position map (d_pwpos) are staged
+//     as the factored model's lv bits and map are
+int stage_exact_generic(Ctx& c, const double* d_t64, double amax, const double* U, bool shared) {
   const size_t S = c.S, E = c.E;
   c.xg_ok = false;
-  if (c.d_xX) {
-    HIPCHK(hipFree(c.d_xX));
-    c.d_xX = nullptr;
-  }
-  if (!c.exact_generic || E > 8192 || !(amax <= 700.0)) return NEMO_OK;
+  c.xg_shared = shared;   // (as detected, covered or not: option "exact_shared")
+  c.exact_form_used = 0;
+  for (double** p : {&c.d_xX, &c.d_xl})
+    if (*p) {
+      HIPCHK(hipFree(*p));
+      *p = nullptr;
+    }
+  if (!c.exact_generic || (!shared && E > 8192) || !(amax <= 700.0)) return NEMO_OK;
   for (size_t k = 0; k < (S + 1) * E; ++k)
     if (!(fabs(U[k]) <= 700.0)) return NEMO_OK;
   std::vector<nemo::host::PairwisePlan> parts;
-  if (!nemo::host::build_pairwise_parts(c.E, parts) || parts.size() != 1 || parts[0].ns > nemo::kExactMaxSlots ||
-      parts[0].nh > 8)
+  if (!nemo::host::build_pairwise_parts(c.E, parts) || parts.size() > (size_t)nemo::kExactMaxParts ||
+      (!shared && parts.size() != 1))
     return NEMO_OK;
+  for (const auto& p : parts)
+    if (p.ns > nemo::kExactMaxSlots || p.nh > 8) return NEMO_OK;
   std::vector<int32_t> dev, meta;
   nemo::host::parts_device_rows(parts, dev, meta);
-  HIPCHK(dalloc(&c.d_xX, S * S * E));
-  HIPCHK(nemo::launch_exact_exp_table(c, d_t64, c.d_xX, c.stream));
+  if (shared) {
+    // parent j's row, exp'd by the kernel the whole table takes
+    HIPCHK(dalloc(&c.d_xX, S * E));
+    for (size_t j = 0; j < S; ++j)
+      HIPCHK(nemo::launch_exact_exp_table(c, d_t64 + ((size_t)nemo::host::shared_row_child((int)j) * S + j) * E,
+                                          c.d_xX + j * E, E, c.stream));
+    std::vector<double> x(S * E), lm1;
+    HIPCHK(nemo::copy_sync(c, x.data(), c.d_xX, S * E * 8, hipMemcpyDeviceToHost));
+    nemo::host::parts_lm1_rows(parts, c.S, c.E, x.data(), lm1);
+    std::vector<int32_t> ppos;
+    nemo::host::parts_positions(parts, c.E, ppos);
+    HIPCHK(dalloc(&c.d_xl, lm1.size()));
+    HIPCHK(dalloc(&c.d_pwpos, ppos.size()));
+    HIPCHK(nemo::copy_sync(c, c.d_xl, lm1.data(), lm1.size() * 8, hipMemcpyHostToDevice));
+    HIPCHK(nemo::copy_sync(c, c.d_pwpos, ppos.data(), ppos.size() * 4, hipMemcpyHostToDevice));
+  } else {
+    HIPCHK(dalloc(&c.d_xX, S * S * E));
+    HIPCHK(nemo::launch_exact_exp_table(c, d_t64, c.d_xX, S * S * E, c.stream));
+  }
   HIPCHK(dalloc(&c.d_pwplan, dev.size()));
   HIPCHK(dalloc(&c.d_pwmeta, meta.size()));
   if (!c.d_xqueue) HIPCHK(dalloc(&c.d_xqueue, 1));
   HIPCHK(nemo::copy_sync(c, c.d_pwplan, dev.data(), dev.size() * 4, hipMemcpyHostToDevice));
   HIPCHK(nemo::copy_sync(c, c.d_pwmeta, meta.data(), meta.size() * 4, hipMemcpyHostToDevice));
   c.pw_ns = nemo::host::parts_slots(parts);
-  c.pw_parts = 1;
+  c.pw_parts = (int)parts.size();
   c.pw_nh = parts[0].nh;
   c.pw_maxrem = parts[0].maxrem;
   c.xg_ok = true;
@@ -465,18 +493,22 @@ extern "C" {
 // context's own non-blocking stream (nemo::copy_sync), so they neither touch
 // the legacy stream nor wait for another engine's capture
 // (tests/test_gpu_parity.py::test_staging_while_another_engine_captures)
-int nemo_stage_tables(nemo_ctx* ctx, const double* U, const double* T) {
+// nemo_stage_tables (T [S][S][E]) and nemo_stage_log_ratios (R [S][E], the
+// model T[i][j] = R[j] for every child i; T null): one staging path from the
+// fp64 table on the device on, so both give the same staged model to the bit
+static int stage_tables(nemo_ctx* ctx, const double* U, const double* T, const double* R) {
   int rc = check_ctx(ctx, false);
   if (rc) return rc;
-  if (!U || !T) return fail(NEMO_ERR_ARG, "null table");
+  if (!U || (!T && !R)) return fail(NEMO_ERR_ARG, "null table");
   Ctx& c = ctx->c;
   const size_t S = c.S, E = c.E, n = S * S * E;
-  // range of the off-diagonal rows (the ones the score reads)
+  // range of the off-diagonal rows (the ones the score reads; of R: every row,
+  // each the off-diagonal row of S - 1 >= 1 children, in T's order)
   double amax = 0.0;
   for (size_t i = 0; i < S; ++i)
     for (size_t j = 0; j < S; ++j) {
-      if (i == j) continue;
-      const double* r = T + (i * S + j) * E;
+      if (i == j || (!T && i != (size_t)nemo::host::shared_row_child((int)j))) continue;   // (R[j]: once)
+      const double* r = T ? T + (i * S + j) * E : R + j * E;
       for (size_t e = 0; e < E; ++e) {
         const double v = r[e];
         if (!isfinite(v)) return fail(NEMO_ERR_ARG, "T[%zu][%zu][%zu] is not finite", i, j, e);
@@ -487,8 +519,11 @@ int nemo_stage_tables(nemo_ctx* ctx, const double* U, const double* T) {
   // and two-valued (nem.py:44-46 builds exactly that); lo_j = its first value
   std::vector<uint64_t> d1;
   std::vector<double> elo, ehi, tlo, thi;
-  bool fact = nemo::host::detect_factored(c.S, c.E, T, d1, elo, ehi, &tlo, &thi);
+  bool fact = T ? nemo::host::detect_factored(c.S, c.E, T, d1, elo, ehi, &tlo, &thi)
+                : nemo::host::detect_factored_rows(c.S, c.E, R, d1, elo, ehi, &tlo, &thi);
   const bool generic = !fact;
+  // a row-shared real-valued table (option exact_generic): R's model is one
+  const bool shared = generic && c.exact_generic && (!T || nemo::host::detect_row_shared(c.S, c.E, T));
   // the product range: four factors of the fast kernels' products stay finite.
   // Option exact_generic: a generic fp64 table may reach past it (a wide
   // table, nemo_internal.h) -- the exact kernels take no products (covered to
@@ -504,7 +539,15 @@ int nemo_stage_tables(nemo_ctx* ctx, const double* U, const double* T) {
   if ((rc = alloc_tables(c))) return rc;
   double* d_t64 = nullptr;
   HIPCHK(hipMalloc((void**)&d_t64, n * sizeof(double)));
-  HIPCHK(hipMemcpyAsync(d_t64, T, n * sizeof(double), hipMemcpyHostToDevice, c.stream));
+  if (T) {
+    HIPCHK(hipMemcpyAsync(d_t64, T, n * sizeof(double), hipMemcpyHostToDevice, c.stream));
+  } else {
+    // R alone crosses: the broadcast table is made on the device (R staged in
+    // the first rows of d_U64, which U overwrites below)
+    HIPCHK(nemo::copy_sync(c, c.d_U64, R, S * E * 8, hipMemcpyHostToDevice));
+    HIPCHK(nemo::launch_broadcast_rows(c, c.d_U64, d_t64, c.stream));
+    HIPCHK(hipStreamSynchronize(c.stream));
+  }
   HIPCHK(nemo::launch_exp_table(c, d_t64, c.stream));
   if (c.dtype == NEMO_F64) {
     HIPCHK(hipMemcpyAsync(c.d_U, U, (S + 1) * E * 8, hipMemcpyHostToDevice, c.stream));
@@ -524,11 +567,21 @@ int nemo_stage_tables(nemo_ctx* ctx, const double* U, const double* T) {
   for (size_t k = 0; k < (S + 1) * E && fact; ++k)
     if (!isfinite(U[k]) || fabs(U[k]) > 1e9) fact = false;
   // a generic table's exact tables (option exact_generic), while T is on the device
-  rc = generic ? stage_exact_generic(c, d_t64, amax, U) : NEMO_OK;
+  rc = generic ? stage_exact_generic(c, d_t64, amax, U, shared) : NEMO_OK;
   const hipError_t fe = hipFree(d_t64);
   if (rc) return rc;
   HIPCHK(fe);
   return stage_factored(ctx, fact, d1, elo, ehi, tlo, thi);
+}
+
+int nemo_stage_tables(nemo_ctx* ctx, const double* U, const double* T) {
+  if (!T) return fail(NEMO_ERR_ARG, "null table");
+  return stage_tables(ctx, U, T, nullptr);
+}
+
+int nemo_stage_log_ratios(nemo_ctx* ctx, const double* U, const double* R) {
+  if (!R) return fail(NEMO_ERR_ARG, "null table");
+  return stage_tables(ctx, U, nullptr, R);
 }
 
 int nemo_stage_knockdown(nemo_ctx* ctx, const uint8_t* D, double A, double B) {
@@ -1675,6 +1728,9 @@ int nemo_get_option(nemo_ctx* ctx, const char* name, int* value) {
   else if (strcmp(name, "exact_lat_waves") == 0) *value = c.exact_lat_waves;
   else if (strcmp(name, "exact_pair_waves") == 0) *value = c.exact_pair_waves;
   else if (strcmp(name, "exact_ok") == 0) *value = nemo::exact_supported(c) ? 1 : 0;
+  else if (strcmp(name, "exact_shared") == 0) *value = !c.factored && c.xg_shared ? 1 : 0;
+  else if (strcmp(name, "exact_rc") == 0) *value = nemo::exact_supported(c) && nemo::exact_rc(c) ? 1 : 0;
+  else if (strcmp(name, "exact_form_used") == 0) *value = c.exact_form_used;
   else if (strcmp(name, "step_host_sum") == 0) *value = c.step_host_sum;
   else if (strcmp(name, "win") == 0) *value = c.win_ok ? 1 : 0;
   else if (strcmp(name, "local_prod") == 0) *value = c.local_prod && c.table_absmax <= 40.0 ? 1 : 0;

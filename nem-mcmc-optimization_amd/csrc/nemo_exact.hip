@@ -242,7 +242,9 @@ __global__ __launch_bounds__(kCellsThreads) void exact_cells_kernel(int S, int E
 // broadcast read per parent), kGU parents' X loads are issued ahead of their
 // logs.  The blocks of one (child, tile) are adjacent over the evaluations and
 // an XCD takes a contiguous range of them (xcd_block, option exact_xcd), so
-// the chains of a batch read the child's X rows from one L2.
+// the chains of a batch read the child's X rows from one L2.  xstride: X's
+// child stride, S E for a table with its own rows per child, 0 for a
+// row-shared one (X [S][E]: every child reads parent j's one row).
 // ---------------------------------------------------------------------------
 constexpr int kGenThreads = 256, kGenU = 4;
 
@@ -260,6 +262,7 @@ __global__ __launch_bounds__(kGenThreads) void exact_cells_generic_kernel(int S,
                                                                           const int32_t* __restrict__ pos,
                                                                           const double* __restrict__ w01,
                                                                           const double* __restrict__ X,
+                                                                          size_t xstride,
                                                                           const double* __restrict__ U,
                                                                           double* __restrict__ cells, int xcd) {
 #pragma clang fp contract(off)
@@ -297,7 +300,7 @@ __global__ __launch_bounds__(kGenThreads) void exact_cells_generic_kernel(int S,
   __syncthreads();
   if (e >= E) return;
   const LdsTabs tb = tabs.view();
-  const double* xi = X + (size_t)i * S * E + e;
+  const double* xi = X + (size_t)i * xstride + e;   // (xstride 0: a row-shared table's one X row per parent)
   double cell = urow[e];
   int q = 0;
   for (; q + kGenU <= np; q += kGenU) {
@@ -363,12 +366,15 @@ __global__ __launch_bounds__(256) void exact_fold_kernel(int S, int E, int batch
 // order weights in place: cell = exp(cell - cs) (nem_order_mcmc.py:92), one
 // thread per cell.  With xa (the fused step's recompute form): also the local
 // optima's a = (lv - 1) * ow (nem_order_mcmc.py:161-162, lv = np.exp(T[i][k])
-// of parent row k) at the element's plan position, [batch][S][plan]
+// of parent row k) at the element's plan position, [batch][S][plan]; xreal (a
+// row-shared real-valued table): lv = X[row][e] itself, the same operations as
+// the stored rows' cval
 __global__ __launch_bounds__(256) void exact_ow_kernel(int S, int E, int batch, double* __restrict__ cells,
                                                        const double* __restrict__ cs, double* __restrict__ xa,
                                                        const int32_t* __restrict__ pwpos, int plan_doubles,
                                                        const double* __restrict__ xlo, const double* __restrict__ xhi,
-                                                       const uint64_t* __restrict__ d1w, int nwords) {
+                                                       const uint64_t* __restrict__ d1w, int nwords,
+                                                       const double* __restrict__ xreal) {
 #pragma clang fp contract(off)
   __shared__ TabsLds tabs;
   tabs.fill_exp(threadIdx.x, blockDim.x);
@@ -383,7 +389,7 @@ __global__ __launch_bounds__(256) void exact_ow_kernel(int S, int E, int batch, 
   const double ow = refmath::svml_exp(cells[g] - cs[b * E + e], tabs.view());
   cells[g] = ow;
   if (xa && row < S) {
-    const double lv = d1bit(d1w, nwords, row, e) ? xhi[row] : xlo[row];
+    const double lv = xreal ? xreal[(size_t)row * E + e] : d1bit(d1w, nwords, row, e) ? xhi[row] : xlo[row];
     xa[(b * S + row) * (size_t)plan_doubles + pwpos[e]] = (lv - 1.0) * ow;
   }
 }
@@ -457,13 +463,25 @@ __global__ __launch_bounds__(256) void exact_seq_sum_kernel(int E, int batch, co
 // kPairs (the slot form): the row set's 16 chain rows stored as 8 rows of
 // element pairs (lane l's elements 2p and 2p + 1 side by side), so one 16-byte
 // load brings two c values; the remainder row as before
+// kReal (with kRc; a row-shared real-valued table, option exact_generic): lv is
+// np.exp(R[k][e]), a real number per element, so s (lv - 1) is s times the
+// parent's plan-ordered lm1 = lv - 1.0 (lp, staged once: Ctx::d_xl) read at the
+// same plan index as a, in place of the select between the two products rslo
+// and rshi.  The stored rows compute s * (lv - 1.0) per element (setup_c's
+// cval) from the same lv, and a = (lv - 1.0) * ow is the order-weight launch's
+// from the same lv and ow, so (1.0 - s a) + s lm1 and a / that are the stored
+// rows' operations on the same operands: the same bits.  No padding guard: a
+// position without an element has a = 0 and lm1 = 0, so c = 0 / (1 + 0) = 0,
+// what a stored row holds there.
 template <int NS, bool kPlan, bool kLat, bool kPair = false, bool kRc = false, bool kCache = false, bool kMP = false,
-          bool kPairs = false>
+          bool kPairs = false, bool kReal = false>
 struct ExactObjective {
   static constexpr int kChain = 16;  // a leaf block of <= 128 elements: <= 16 per chain
   static constexpr int kRows = kChain + 1;
   static constexpr bool kPairsLayout = kPairs;
+  static constexpr bool kRealRows = kReal;
   const double* cp;
+  const double* lp = nullptr;   // kReal: the parent's lm1 rows (plan order, as cp)
   // kCache (the latency form's recompute rows, 2 waves per SIMD): the lane's
   // c values made once per optimum (fill_cache) and held in registers through
   // the optimiser, instead of recomputed from the a rows every evaluation --
@@ -520,6 +538,11 @@ struct ExactObjective {
   __device__ __forceinline__ double rc_c(int u, int m, bool real) const {
 #pragma clang fp contract(off)
     const double a = cp[(u * kRows + m) * kWave + lane];
+    if (kReal) {
+      const double sl = rs * lp[(u * kRows + m) * kWave + lane];
+      const double bd = (1.0 - rs * a) + sl;
+      return a / bd;
+    }
     const double sl = ((rbits[kRc ? u : 0] >> m) & 1u) ? rshi : rslo;
     const double bd = (1.0 - rs * a) + sl;
     const double c = a / bd;
@@ -726,6 +749,7 @@ struct ExactObjective {
       // its own wave plan and added to the running sum in order
       const int32_t* pl0 = pl;
       const double* cp0 = cp;
+      const double* lp0 = lp;
       const int nh0 = nh, mr0 = maxrem;
       double q0 = 0.0, q1 = 0.0;
       for (int p = 0; p < nparts; ++p) {
@@ -733,7 +757,8 @@ struct ExactObjective {
         nh = pmeta[2 * p];
         maxrem = pmeta[2 * p + 1];
         if (kPlan) cp = cp0 + (size_t)p * NS * kRows * kWave;
-        if (kRc) {
+        if (kReal) lp = lp0 + (size_t)p * NS * kRows * kWave;
+        if (kRc && !kReal) {
 #pragma unroll
           for (int u = 0; u < NS; ++u) rbits[kRc ? u : 0] = xbk[((size_t)p * NS + u) * kWave + lane];
         }
@@ -749,6 +774,7 @@ struct ExactObjective {
       }
       pl = pl0;
       cp = cp0;
+      lp = lp0;
       nh = nh0;
       maxrem = mr0;
       s0 = q0;
@@ -813,7 +839,12 @@ struct CArgs {
   double* sbuf = nullptr;
   // a generic table (option exact_generic): X = np.exp(T) [S][S][E]; the
   // stored rows take lv = X[i][k][e] in place of the two-valued lookup
+  // (xgs: X's child stride, S E; 0 for a row-shared table's X [S][E])
   const double* xg = nullptr;
+  size_t xgs = 0;
+  // kReal (a row-shared generic table's recompute rows): lv - 1.0 in plan
+  // order, [S][pd]
+  const double* xl = nullptr;
 };
 
 // The persistent form (option exact_persist): resident blocks whose waves take
@@ -836,6 +867,11 @@ __device__ __forceinline__ void setup_c(Obj& obj, const CArgs& ca, int S, int E,
   constexpr size_t kPlanD = (size_t)NS * Obj::kRows * kWave;   // (one part: the stored form)
   if (kRc) {
     obj.cp = ca.xa + ((size_t)b * S + k) * ca.pd;
+    if (Obj::kRealRows) {   // (no lv bits: s (lv - 1) from the parent's lm1 rows)
+      obj.lp = ca.xl + (size_t)k * ca.pd;
+      obj.rs = s;
+      return;
+    }
     obj.xbk = ca.xbits + (size_t)k * NS * ca.nparts * kWave;
 #pragma unroll
     for (int u = 0; u < NS; ++u) obj.rbits[kRc ? u : 0] = obj.xbk[(size_t)u * kWave + lane];
@@ -878,12 +914,14 @@ __device__ __forceinline__ void setup_slot(Obj& obj, const CArgs& ca, int S, int
                                            double lvhi, int lane, double* __restrict__ rows) {
 #pragma clang fp contract(off)
   const double* xa = ca.xa + ((size_t)b * S + k) * ca.pd;
-  const uint32_t* xb = ca.xbits + (size_t)k * NS * kWave;
+  constexpr bool kReal = Obj::kRealRows;   // (rc_c's real-valued case: lm1 rows, no bits, no padding guard)
+  const double* xl = kReal ? ca.xl + (size_t)k * ca.pd : nullptr;
+  const uint32_t* xb = kReal ? nullptr : ca.xbits + (size_t)k * NS * kWave;
   const double rslo = s * (lvlo - 1.0), rshi = s * (lvhi - 1.0);
-  const bool pad_guard = lb::uni(1.0 + rslo == 0.0);
+  const bool pad_guard = !kReal && lb::uni(1.0 + rslo == 0.0);
 #pragma unroll
   for (int u = 0; u < NS; ++u) {
-    const uint32_t bits = xb[(size_t)u * kWave + lane];
+    const uint32_t bits = kReal ? 0u : xb[(size_t)u * kWave + lane];
     const int cu = obj.cnt(u), ru = obj.rem(u);
 #pragma unroll 4
     for (int m = 0; m <= Obj::kChain; ++m) {
@@ -893,7 +931,9 @@ __device__ __forceinline__ void setup_slot(Obj& obj, const CArgs& ca, int S, int
                             ? (size_t)u * Obj::kRows * kWave + ((size_t)(m >> 1) * kWave + lane) * 2 + (m & 1)
                             : at;
       const double a = xa[at];
-      const double sl = ((bits >> m) & 1u) ? rshi : rslo;
+      double sl;
+      if constexpr (kReal) sl = s * xl[at];
+      else sl = ((bits >> m) & 1u) ? rshi : rslo;
       const double bd = (1.0 - s * a) + sl;
       const double c = a / bd;
       const bool real = m < Obj::kChain ? m < cu : ru >= 0;
@@ -910,7 +950,9 @@ __device__ __forceinline__ void setup_slot(Obj& obj, const CArgs& ca, int S, int
 // loop on the latency form's register c cache, at NEMO_EXACT_CT_WAVES per SIMD
 // kSlot (form 7, the slot form): the throughput form reading c from the
 // resident wave's row set made by setup_slot (persistent launches only)
-template <int NS, bool kLat, bool kRc, bool kCt = false, bool kMP = false, bool kSlot = false>
+// kReal (with kRc): a row-shared real-valued table's recompute rows
+// (ExactObjective's kReal; xlo, xhi, d1w and ca.xbits are not read)
+template <int NS, bool kLat, bool kRc, bool kCt = false, bool kMP = false, bool kSlot = false, bool kReal = false>
 __global__ __launch_bounds__(kExactWaves * kWave)
 __attribute__((amdgpu_waves_per_eu(kSlot ? NEMO_EXACT_SLOT_WAVES : kCt ? NEMO_EXACT_CT_WAVES : kLat ? 2 : NEMO_EXACT_TPUT_WAVES,
                                    kSlot ? NEMO_EXACT_SLOT_WAVES : kCt ? NEMO_EXACT_CT_WAVES : kLat ? 2 : NEMO_EXACT_TPUT_WAVES))) void local_opt_exact_kernel(
@@ -954,7 +996,7 @@ __attribute__((amdgpu_waves_per_eu(kSlot ? NEMO_EXACT_SLOT_WAVES : kCt ? NEMO_EX
   const double* owk = ow + ((size_t)b * (S + 1) + k) * E;
   const long long t_start = ca.trace ? (long long)wall_clock64() : 0;
   using Obj = ExactObjective<NS, true, kLat, false, kRc && !kSlot, (kLat || kCt) && kRc && NEMO_EXACT_CCACHE, kMP,
-                             kSlot && NEMO_EXACT_SLOT_PAIRS>;
+                             kSlot && NEMO_EXACT_SLOT_PAIRS, kReal>;
   Obj obj;
   obj.tb = tabs.view();
   obj.pl = pl;
@@ -964,11 +1006,12 @@ __attribute__((amdgpu_waves_per_eu(kSlot ? NEMO_EXACT_SLOT_WAVES : kCt ? NEMO_EX
   obj.anc = anc[idx];
   obj.load_plan();
   if constexpr (kSlot)
-    setup_slot<Obj, NS>(obj, ca, S, b, k, s, xlo[k], xhi[k], lane,
+    setup_slot<Obj, NS>(obj, ca, S, b, k, s, kReal ? 0.0 : xlo[k], kReal ? 0.0 : xhi[k], lane,
                         ca.sbuf + ((size_t)blockIdx.x * kExactWaves + wv) * ca.pd);
   else
-    setup_c<Obj, NS, kRc>(obj, ca, S, E, b, k, (size_t)gw, s, ca.xg ? 0.0 : xlo[k], ca.xg ? 0.0 : xhi[k], owk, d1w,
-                          nwords, lane, ~0u, ca.xg ? ca.xg + ((size_t)i * S + k) * E : nullptr);
+    setup_c<Obj, NS, kRc>(obj, ca, S, E, b, k, (size_t)gw, s, kReal || ca.xg ? 0.0 : xlo[k],
+                          kReal || ca.xg ? 0.0 : xhi[k], owk, d1w, nwords, lane, ~0u,
+                          ca.xg ? ca.xg + (size_t)i * ca.xgs + (size_t)k * E : nullptr);
   obj.nparts = ca.nparts;
   obj.plg = ca.plan;
   obj.pmeta = ca.pmeta;
@@ -1081,7 +1124,7 @@ __global__ __launch_bounds__(2 * kWave) __attribute__((amdgpu_waves_per_eu(4, 4)
   // this wave's slots' rows (it alone reads them)
   setup_c<Obj, NS, kRc>(obj, ca, S, E, b, k, (size_t)gw, s, ca.xg ? 0.0 : xlo[k], ca.xg ? 0.0 : xhi[k], owk, d1w,
                         nwords, lane, wv ? 0xaaaaaaaau : 0x55555555u,
-                        ca.xg ? ca.xg + ((size_t)i * S + k) * E : nullptr);
+                        ca.xg ? ca.xg + (size_t)i * ca.xgs + (size_t)k * E : nullptr);
   LbxState& st = *reinterpret_cast<LbxState*>(lst_raw[wv]);
   lbx_init(st, s);
   long long c_obj = 0, c_ctl = 0, tc = ca.trace ? (long long)clock64() : 0;   // (trace: shader cycles)
@@ -1531,12 +1574,11 @@ hipError_t launch_refmath_probe(int fn, int n, const double* d_x, const double* 
 }
 
 bool exact_supported(const Ctx& c) {
-  if (exact_generic(c)) return c.d_xX && c.d_pwplan;
+  if (exact_generic(c)) return c.d_xX && c.d_pwplan && (!c.xg_shared || (c.d_xl && c.d_pwpos));
   return c.factored && c.exact_ok && c.d_xlo && c.d_pwplan;
 }
 
-hipError_t launch_exact_exp_table(Ctx& c, const double* d_T64, double* d_X, hipStream_t st) {
-  const size_t n = (size_t)c.S * c.S * c.E;
+hipError_t launch_exact_exp_table(Ctx&, const double* d_T64, double* d_X, size_t n, hipStream_t st) {
   const int blocks = (int)std::min<size_t>((n + 255) / 256, 8192);
   exact_exp_table_kernel<<<blocks, 256, 0, st>>>(n, d_T64, d_X);
   return hipGetLastError();
@@ -1556,8 +1598,9 @@ hipError_t launch_exact_eval(Ctx& c, int batch, int cap, const int32_t* d_pos, c
     const size_t nblk = (size_t)(S + 1) * ntiles * batch;
     if (nblk > 0x7fffffffu) return hipErrorInvalidValue;
     exact_cells_generic_kernel<<<dim3((unsigned)nblk), threads, 0, st>>>(S, E, batch, ntiles, cap >= S - 1 ? 0 : cap,
-                                                                         d_pos, d_w01, c.d_xX, c.d_U64, d_cells,
-                                                                         c.exact_xcd);
+                                                                         d_pos, d_w01, c.d_xX,
+                                                                         c.xg_shared ? 0 : (size_t)S * E, c.d_U64,
+                                                                         d_cells, c.exact_xcd);
   } else {
     // one wave per group of 4 D1 words, at most kCellsThreads / 64 waves; 8
     // children per block once the batch alone fills the chip
@@ -1578,7 +1621,7 @@ hipError_t launch_exact_eval(Ctx& c, int batch, int cap, const int32_t* d_pos, c
     const size_t ncell = (size_t)batch * (S + 1) * E;
     exact_ow_kernel<<<(unsigned)((ncell + 255) / 256), 256, 0, st>>>(
         S, E, batch, d_cells, d_cs, d_xa, c.d_pwpos, (int)exact_plan_doubles(c), c.d_xlo, c.d_xhi, c.d_D1w,
-        c.nwords);
+        c.nwords, exact_shared(c) ? c.d_xX : nullptr);
     err = hipGetLastError();
   }
   if (err != hipSuccess || !d_ll) return err;
@@ -1631,8 +1674,25 @@ int lo_resident(int form) {
   return resident_blocks<local_opt_exact_kernel<NS, false, kRc>>(kExactWaves * kWave);
 }
 
+// a row-shared real-valued table's recompute rows (kReal): the latency form
+// with its cache (1), the cached throughput form (4), the throughput form on
+// several plan parts (6), the slot form (7), else the throughput form (2)
 template <int NS>
-int lo_resident_ns(int form, bool rc) {
+int lo_resident_real(int form) {
+  if (form == 1)
+    return resident_blocks<local_opt_exact_kernel<NS, true, true, false, false, false, true>>(kExactWaves * kWave);
+  if (form == 4)
+    return resident_blocks<local_opt_exact_kernel<NS, false, true, true, false, false, true>>(kExactWaves * kWave);
+  if (form == 6)
+    return resident_blocks<local_opt_exact_kernel<NS, false, true, false, true, false, true>>(kExactWaves * kWave);
+  if (form == 7)
+    return resident_blocks<local_opt_exact_kernel<NS, false, true, false, false, true, true>>(kExactWaves * kWave);
+  return resident_blocks<local_opt_exact_kernel<NS, false, true, false, false, false, true>>(kExactWaves * kWave);
+}
+
+template <int NS>
+int lo_resident_ns(int form, bool rc, bool real = false) {
+  if (real) return lo_resident_real<NS>(form);
   if (form == 5) {
     if constexpr (NS <= 2) return resident_blocks<local_opt_exact_dual_kernel<NS>>(kExactWaves * kWave);
     return 0;
@@ -1669,7 +1729,22 @@ void launch_lo(const LoArgs& a, int form, dim3 grid, hipStream_t st) {
 }
 
 template <int NS>
-void launch_lo_ns(const LoArgs& a, int form, bool rc, dim3 grid, hipStream_t st) {
+void launch_lo_real(const LoArgs& a, int form, dim3 grid, hipStream_t st) {
+#define NEMO_LO_REAL(...)                                                                                        \
+  local_opt_exact_kernel<NS, __VA_ARGS__, true><<<grid, kExactWaves * kWave, 0, st>>>(                           \
+      a.S, a.E, a.npairs, a.nchains, a.pairs, a.w01, a.anc, a.ow, a.xlo, a.xhi, a.d1w, a.nwords, a.plan, a.nh,    \
+      a.maxrem, a.sig0, a.sig1, a.wnew, a.wdag, a.info, a.ca, a.lo_blocks, a.fin)
+  if (form == 1) NEMO_LO_REAL(true, true, false, false, false);
+  else if (form == 4) NEMO_LO_REAL(false, true, true, false, false);
+  else if (form == 6) NEMO_LO_REAL(false, true, false, true, false);
+  else if (form == 7) NEMO_LO_REAL(false, true, false, false, true);
+  else NEMO_LO_REAL(false, true, false, false, false);
+#undef NEMO_LO_REAL
+}
+
+template <int NS>
+void launch_lo_ns(const LoArgs& a, int form, bool rc, bool real, dim3 grid, hipStream_t st) {
+  if (real) return launch_lo_real<NS>(a, form, grid, st);
   if (form == 5) {
     if constexpr (NS <= 2)
       local_opt_exact_dual_kernel<NS><<<grid, kExactWaves * kWave, 0, st>>>(
@@ -1685,15 +1760,16 @@ void launch_lo_ns(const LoArgs& a, int form, bool rc, dim3 grid, hipStream_t st)
 
 size_t exact_slot_doubles(const Ctx& c) {
   int res = 0;
+  const bool real = exact_shared(c);
   switch (c.pw_ns) {
-    case 1: res = lo_resident_ns<1>(7, true); break;
-    case 2: res = lo_resident_ns<2>(7, true); break;
-    case 3: res = lo_resident_ns<3>(7, true); break;
-    case 4: res = lo_resident_ns<4>(7, true); break;
-    case 5: res = lo_resident_ns<5>(7, true); break;
-    case 6: res = lo_resident_ns<6>(7, true); break;
-    case 7: res = lo_resident_ns<7>(7, true); break;
-    case 8: res = lo_resident_ns<8>(7, true); break;
+    case 1: res = lo_resident_ns<1>(7, true, real); break;
+    case 2: res = lo_resident_ns<2>(7, true, real); break;
+    case 3: res = lo_resident_ns<3>(7, true, real); break;
+    case 4: res = lo_resident_ns<4>(7, true, real); break;
+    case 5: res = lo_resident_ns<5>(7, true, real); break;
+    case 6: res = lo_resident_ns<6>(7, true, real); break;
+    case 7: res = lo_resident_ns<7>(7, true, real); break;
+    case 8: res = lo_resident_ns<8>(7, true, real); break;
     default: return 0;
   }
   return (size_t)std::max(res, 1) * kExactWaves * exact_plan_doubles(c);
@@ -1713,13 +1789,22 @@ hipError_t launch_local_opt_exact(Ctx& c, int nchains, int npairs, const int32_t
   // crossover between 8 and 12 chains, profiles/r6/r6j_forms_ab.txt -- or the
   // throughput form where the slot form does not apply; the pair form for few
   // optima with two slots or more
+  // A row-shared real-valued table's recompute rows (`real`) follow the same
+  // rule at a quarter of the threshold: at 64 x 2000 the latency form is ahead
+  // at 1 chain (0.43 against 0.45 ms per step) and the slot form from 4 chains
+  // on (0.59 against 0.61; 8: 0.90 against 1.02; 16: 1.54 against 1.78;
+  // profiles/generic/forms_by_chains.json)
+  const bool real = exact_shared(c) && rc;
   int form = c.exact_form;
-  if (form == 0) form = nw <= c.exact_lat_waves ? 1 : 7;
+  if (form == 0) form = nw <= (real ? c.exact_lat_waves / 4 : c.exact_lat_waves) ? 1 : 7;
   // (auto: the pair form up to 3 slots; from 4 its LDS and registers hold it
   // to 1-2 waves per SIMD)
   if (c.pw_ns >= 2 && (c.exact_form == 3 || (c.exact_form == 0 && nw <= c.exact_pair_waves && c.pw_ns <= 3)))
     form = 3;
   if (c.pw_ns < 2 && form == 3) form = 2;
+  // a row-shared real-valued table's recompute rows: the pair and dual forms
+  // have no real-valued instance and run as the throughput form
+  if (real && (form == 3 || form == 5)) form = 2;
   // two plan parts (E > 8192): the throughput form, whose objective reads
   // each part's plan from global memory and recomputes c per evaluation
   if (c.pw_parts > 1) form = 6;
@@ -1735,14 +1820,14 @@ hipError_t launch_local_opt_exact(Ctx& c, int nchains, int npairs, const int32_t
   if (persist) {
     int res = 0;
     switch (c.pw_ns) {
-      case 1: res = lo_resident_ns<1>(form, rc); break;
-      case 2: res = lo_resident_ns<2>(form, rc); break;
-      case 3: res = lo_resident_ns<3>(form, rc); break;
-      case 4: res = lo_resident_ns<4>(form, rc); break;
-      case 5: res = lo_resident_ns<5>(form, rc); break;
-      case 6: res = lo_resident_ns<6>(form, rc); break;
-      case 7: res = lo_resident_ns<7>(form, rc); break;
-      case 8: res = lo_resident_ns<8>(form, rc); break;
+      case 1: res = lo_resident_ns<1>(form, rc, real); break;
+      case 2: res = lo_resident_ns<2>(form, rc, real); break;
+      case 3: res = lo_resident_ns<3>(form, rc, real); break;
+      case 4: res = lo_resident_ns<4>(form, rc, real); break;
+      case 5: res = lo_resident_ns<5>(form, rc, real); break;
+      case 6: res = lo_resident_ns<6>(form, rc, real); break;
+      case 7: res = lo_resident_ns<7>(form, rc, real); break;
+      case 8: res = lo_resident_ns<8>(form, rc, real); break;
       default: return hipErrorInvalidValue;
     }
     lo_blocks = std::min(lo_blocks, std::max(res, 1));
@@ -1788,17 +1873,21 @@ hipError_t launch_local_opt_exact(Ctx& c, int nchains, int npairs, const int32_t
   a.ca.pmeta = c.d_pwmeta;
   a.ca.pd = exact_plan_doubles(c);
   a.ca.sbuf = c.d_xsbuf;
-  a.ca.xg = exact_generic(c) ? c.d_xX : nullptr;   // (stored rows: exact_rc is false for a generic table)
+  // (stored rows: exact_rc is false for a generic table with its own rows per child)
+  a.ca.xg = exact_generic(c) ? c.d_xX : nullptr;
+  a.ca.xgs = c.xg_shared ? 0 : (size_t)c.S * c.E;
+  a.ca.xl = real ? c.d_xl : nullptr;
+  c.exact_form_used = form;
   c.xtrace_n = a.ca.trace ? nw : 0;
   switch (c.pw_ns) {
-    case 1: launch_lo_ns<1>(a, form, rc, grid, st); break;
-    case 2: launch_lo_ns<2>(a, form, rc, grid, st); break;
-    case 3: launch_lo_ns<3>(a, form, rc, grid, st); break;
-    case 4: launch_lo_ns<4>(a, form, rc, grid, st); break;
-    case 5: launch_lo_ns<5>(a, form, rc, grid, st); break;
-    case 6: launch_lo_ns<6>(a, form, rc, grid, st); break;
-    case 7: launch_lo_ns<7>(a, form, rc, grid, st); break;
-    case 8: launch_lo_ns<8>(a, form, rc, grid, st); break;
+    case 1: launch_lo_ns<1>(a, form, rc, real, grid, st); break;
+    case 2: launch_lo_ns<2>(a, form, rc, real, grid, st); break;
+    case 3: launch_lo_ns<3>(a, form, rc, real, grid, st); break;
+    case 4: launch_lo_ns<4>(a, form, rc, real, grid, st); break;
+    case 5: launch_lo_ns<5>(a, form, rc, real, grid, st); break;
+    case 6: launch_lo_ns<6>(a, form, rc, real, grid, st); break;
+    case 7: launch_lo_ns<7>(a, form, rc, real, grid, st); break;
+    case 8: launch_lo_ns<8>(a, form, rc, real, grid, st); break;
     default: return hipErrorInvalidValue;
   }
   if (e1) {

@@ -15,6 +15,7 @@
 #include <chrono>
 #include <cmath>
 #include <condition_variable>
+#include <cstring>
 #include <deque>
 #include <functional>
 #include <memory>
@@ -53,9 +54,11 @@ inline int first_bad_pos_row(const int32_t* pos, int batch, int S) {
 // bit d1[j][e] = 1 where it takes the other value hi_j.  T [S][S][E];
 // d1 [S][nwords] (nwords = ceil(E / 64)), elo / ehi [S] = exp(lo_j), exp(hi_j).
 // Returns false (outputs unspecified) when T lacks that structure.
+// rows: T is R [S][E] itself, the one row every child shares per parent
+// (detect_factored_rows) -- nothing to compare, the same two-valued test.
 inline bool detect_factored(int S, int E, const double* T, std::vector<uint64_t>& d1, std::vector<double>& elo,
                             std::vector<double>& ehi, std::vector<double>* tlo = nullptr,
-                            std::vector<double>* thi = nullptr) {
+                            std::vector<double>* thi = nullptr, bool rows = false) {
   const int nwords = (E + 63) / 64;
   d1.assign((size_t)S * nwords, 0ull);
   elo.assign(S, 0.0);
@@ -64,8 +67,8 @@ inline bool detect_factored(int S, int E, const double* T, std::vector<uint64_t>
   if (thi) thi->assign(S, 0.0);
   for (int j = 0; j < S; ++j) {
     const int i0 = (j == 0) ? 1 : 0;
-    const double* L = T + ((size_t)i0 * S + j) * E;
-    for (int i = 0; i < S; ++i)
+    const double* L = rows ? T + (size_t)j * E : T + ((size_t)i0 * S + j) * E;
+    for (int i = 0; i < S && !rows; ++i)
       if (i != j && i != i0 && !std::equal(L, L + E, T + ((size_t)i * S + j) * E)) return false;
     const double lo = L[0];
     double hi = lo;
@@ -84,6 +87,28 @@ inline bool detect_factored(int S, int E, const double* T, std::vector<uint64_t>
     ehi[j] = std::exp(hi);
     if (tlo) (*tlo)[j] = lo;
     if (thi) (*thi)[j] = hi;
+  }
+  return true;
+}
+
+// detect_factored on the model T[i][j] = R[j] (every i), from R [S][E] alone:
+// the outputs detect_factored gives on the broadcast table
+inline bool detect_factored_rows(int S, int E, const double* R, std::vector<uint64_t>& d1, std::vector<double>& elo,
+                                 std::vector<double>& ehi, std::vector<double>* tlo = nullptr,
+                                 std::vector<double>* thi = nullptr) {
+  return detect_factored(S, E, R, d1, elo, ehi, tlo, thi, true);
+}
+
+// A row-shared table: T[i][j] bit-identical for every child i != j, for each
+// parent j -- real-valued per-effect log ratios (TableModel.from_log_ratios),
+// T[i][j] = R[j].  Parent j's row is then T[shared_row_child(j)][j].
+inline int shared_row_child(int j) { return j == 0 ? 1 : 0; }
+inline bool detect_row_shared(int S, int E, const double* T) {
+  if (S < 2) return false;
+  for (int j = 0; j < S; ++j) {
+    const double* L = T + ((size_t)shared_row_child(j) * S + j) * E;
+    for (int i = 0; i < S; ++i)
+      if (i != j && std::memcmp(L, T + ((size_t)i * S + j) * E, (size_t)E * sizeof(double)) != 0) return false;
   }
   return true;
 }
@@ -302,6 +327,21 @@ inline void parts_lv_bits(const std::vector<PairwisePlan>& parts, int S, const u
         for (int l = 0; l < 64; ++l)
           bits[((size_t)k * ns + p * nsp + u) * 64 + l] = b[((size_t)k * parts[p].ns + u) * 64 + l];
   }
+}
+
+// A row-shared real-valued table's lv - 1 in plan order (the recompute rows'
+// second operand, nemo_exact.hip rc_c): X [S][E] = np.exp(R) in numpy's bits,
+// out [S][pd], pd = parts x slots x 17 x 64 doubles (one plan-ordered row set
+// over all parts): X[k][e] - 1.0 at pos[e] (parts_positions) of row k, 0
+// where the plan has no element
+inline void parts_lm1_rows(const std::vector<PairwisePlan>& parts, int S, int E, const double* X,
+                           std::vector<double>& out) {
+  const size_t pd = parts.size() * (size_t)parts_slots(parts) * 17 * 64;
+  std::vector<int32_t> pos;
+  parts_positions(parts, E, pos);
+  out.assign((size_t)S * pd, 0.0);
+  for (int k = 0; k < S; ++k)
+    for (int e = 0; e < E; ++e) out[(size_t)k * pd + (size_t)pos[(size_t)e]] = X[(size_t)k * E + e] - 1.0;
 }
 
 // the two addition chains of compute_scores (nem.py:25-34), in its order:

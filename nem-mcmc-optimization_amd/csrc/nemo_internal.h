@@ -119,7 +119,8 @@ struct Ctx {
   // the local-optimum kernel's form: 0 auto (the pair form up to
   // exact_pair_waves optima, none by default; the latency form -- its c values
   // held in registers -- up to exact_lat_waves, ~10 C3 chains, measured best
-  // from 1 to 8 chains; the slot form beyond, best from 12), 1 latency, 2
+  // from 1 to 8 chains; the slot form beyond, best from 12; a row-shared
+  // real-valued table: a quarter of that threshold), 1 latency, 2
   // throughput, 3 pair, 4 cached throughput, 5 dual, 7 slot
   int exact_form = 0;
   int exact_lat_waves = 20000;
@@ -167,12 +168,21 @@ struct Ctx {
   int xtrace_n = 0;                // optima the last traced launch recorded
   // option "exact_generic" (0 default; set before staging): nemo_stage_tables
   // also stages a generic (not factorable) table for the exact kernels -- X =
-  // np.exp(T) in numpy's bits and the wave plan of E -- when E <= 8192 (one
-  // numpy buffer: the stored c rows serve one plan part) and max|T|, max|U| <=
-  // 700 (inside the SVML exp's fast path)
+  // np.exp(T) in numpy's bits and the wave plan of E -- when max|T|, max|U| <=
+  // 700 (inside the SVML exp's fast path) and E <= 8192 (one numpy buffer: the
+  // stored c rows serve one plan part), or, for a row-shared table (xg_shared),
+  // E within the factored model's plans (kExactMaxParts buffers)
   int exact_generic = 0;
   bool xg_ok = false;              // the staged generic table is covered
-  double* d_xX = nullptr;          // [S][S][E] numpy's exp(T) (refmath::svml_exp)
+  // the staged generic table is row-shared (host::detect_row_shared: T[i][j] =
+  // R[j] for every child, TableModel.from_log_ratios): X holds one row per
+  // parent, and the local optima have per-parent recompute rows as the
+  // factored model's, with lv - 1 a real number per element (d_xl) in place of
+  // the two values picked by a bit
+  bool xg_shared = false;
+  double* d_xX = nullptr;          // numpy's exp(T) (refmath::svml_exp): [S][S][E], row-shared [S][E]
+  double* d_xl = nullptr;          // row-shared: [S][exact_plan_doubles] lv - 1.0 in plan order, 0 at padding
+  int exact_form_used = 0;         // option "exact_form_used" (get): the form the last exact local optima ran
 
   // worst-case |ll error| of the fixed-point kernels (nemo_host.h):
   // fx_colsum[k] = sum_e min(colbits_e, k) over the staged D1 bits; auto takes
@@ -305,11 +315,18 @@ size_t exact_slot_doubles(const Ctx& c);   // the slot form's row sets: its resi
 // table; every other fast kernel that reads exp(T) refuses it (nemo_abi.cpp)
 constexpr double kProductRangeF64 = 170.0, kProductRangeF32 = 20.0, kWideTableMax = 705.0;
 inline bool wide_table(const Ctx& c) { return c.dtype == 0 && c.table_absmax > kProductRangeF64; }
-// (a generic table has no a rows to recompute from: always the stored form)
+// (a generic table with its own rows per child has no a rows to recompute
+// from: always the stored form; a row-shared one follows the factored rule)
 inline bool exact_generic(const Ctx& c) { return !c.factored && c.xg_ok; }
-inline bool exact_rc(const Ctx& c) { return !exact_generic(c) && (c.exact_cform == 1 || c.pw_parts > 1); }
-// X = np.exp(T) of a generic table in numpy's bits, [S][S][E] from the fp64 host layout
-hipError_t launch_exact_exp_table(Ctx& c, const double* d_T64, double* d_X, hipStream_t st);
+inline bool exact_shared(const Ctx& c) { return exact_generic(c) && c.xg_shared; }
+inline bool exact_rc(const Ctx& c) {
+  return (!exact_generic(c) || c.xg_shared) && (c.exact_cform == 1 || c.pw_parts > 1);
+}
+// X = np.exp(T) of a generic table in numpy's bits: n values of the fp64 table
+// d_T64 into d_X (the whole [S][S][E] table, or one [E] row of a row-shared one)
+hipError_t launch_exact_exp_table(Ctx& c, const double* d_T64, double* d_X, size_t n, hipStream_t st);
+// the fp64 device table T[i][j] = R[j] for every child i, from R [S][E] (nemo_stage_log_ratios)
+hipError_t launch_broadcast_rows(Ctx& c, const double* d_R, double* d_T64, hipStream_t st);
 // eval in the reference's order: cells into d_cells [batch][S+1][E] (with
 // want_ow: replaced by the order weights), cs into d_cs [batch][E], ll into
 // d_ll (nullable: left to the caller)

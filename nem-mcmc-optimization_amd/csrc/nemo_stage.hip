@@ -63,7 +63,23 @@ __global__ void cast_f32_kernel(size_t n, const double* __restrict__ in, float* 
     out[k] = (float)in[k];
 }
 
+// the table of per-effect log ratios R [S][E], T[i][j] = R[j] for every child
+// i (TableModel.from_log_ratios): one block per row (i, j), threads over effects
+__global__ void broadcast_rows_kernel(int S, int E, const double* __restrict__ R, double* __restrict__ T) {
+  const int j = blockIdx.x % S;
+  const double* in = R + (size_t)j * E;
+  double* out = T + (size_t)blockIdx.x * E;
+  for (int e = threadIdx.x; e < E; e += blockDim.x) out[e] = in[e];
+}
+
 }  // namespace
+
+hipError_t launch_broadcast_rows(Ctx& c, const double* d_R, double* d_T64, hipStream_t st) {
+  const int S = c.S, E = c.E;
+  const int threads = E >= 256 ? 256 : ((E + kWave - 1) / kWave) * kWave;
+  broadcast_rows_kernel<<<S * S, threads, 0, st>>>(S, E, d_R, d_T64);
+  return hipGetLastError();
+}
 
 hipError_t launch_knockdown_tables(Ctx& c, const uint8_t* d_D, const double* d_chains, double A,
                                    double B, hipStream_t st) {

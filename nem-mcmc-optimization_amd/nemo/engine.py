@@ -34,8 +34,9 @@ class Engine:
 
     ``exact_generic=True`` (option ``exact_generic``, set before staging):
     real-valued tables that are not factorable are staged for the
-    reference-arithmetic kernels too -- covered for E <= 8192 and max|T|,
-    max|U| <= 700 (``exact_status``); a factorable table is unaffected.
+    reference-arithmetic kernels too -- covered for max|T|, max|U| <= 700 and
+    E <= 8192, or E <= 524288 when every child shares parent j's row
+    (``from_log_ratios``; ``exact_status``); a factorable table is unaffected.
     """
 
     def __init__(self, U, T, device: int = 0, dtype: str = "f64", exact_generic: bool = False):
@@ -76,6 +77,28 @@ class Engine:
                                                float(A), float(B)))
         return self
 
+    @classmethod
+    def from_log_ratios(cls, R, U=None, device: int = 0, dtype: str = "f64",
+                        exact_generic: bool = True) -> "Engine":
+        """The model of per-effect log-likelihood ratios R (S, E), T[i][j] =
+        R[j] for every child i (``TableModel.from_log_ratios``), staged from R
+        alone (``nemo_stage_log_ratios``): the same staged tables as
+        ``Engine(U, T, exact_generic=...)`` with the broadcast T, without the
+        S*S*E host table.  ``U`` defaults to ``[R; 0]``."""
+        R = f64(R)
+        if R.ndim != 2:
+            raise ValueError(f"R must be (S, E), got {R.shape}")
+        s, e = R.shape
+        U = np.vstack([R, np.zeros((1, e))]) if U is None else f64(U)
+        if U.shape != (s + 1, e):
+            raise ValueError(f"U must be ({s + 1}, {e}), got {U.shape}")
+        self = cls.__new__(cls)
+        self._create(s, e, device, dtype)
+        if exact_generic:
+            self.set_option("exact_generic", 1)
+        check(_lib.load().nemo_stage_log_ratios(self._ctx, ptr(U), ptr(R)))
+        return self
+
     # -- cached engines per model -----------------------------------------
     @classmethod
     def for_nem(cls, nem, device: int = 0, dtype: str = "f64") -> "Engine":
@@ -98,13 +121,19 @@ class Engine:
     def for_model(cls, model, device: int = 0, dtype: str = "f64", exact_generic: bool = True) -> "Engine":
         """The engine of a table model (``nemo.nem.TableModel``: ``U`` and
         ``get_score_tables``), one per device, dtype and ``exact_generic``,
-        cached on the model as ``for_nem`` caches a NEM's."""
+        cached on the model as ``for_nem`` caches a NEM's.  A model that
+        holds its log ratios (``TableModel.from_log_ratios``: ``R``) is staged
+        from them (``from_log_ratios``), its tables never built."""
         cache = model.__dict__.setdefault("_nemo_engines", {})
         key = (device, dtype, bool(exact_generic))
         eng = cache.get(key)
         if eng is None:
-            t = np.asarray(model.get_score_tables(None), dtype=np.float64)
-            eng = cls(model.U, t, device=device, dtype=dtype, exact_generic=exact_generic)
+            if getattr(model, "R", None) is not None:
+                eng = cls.from_log_ratios(model.R, model.U, device=device, dtype=dtype,
+                                          exact_generic=exact_generic)
+            else:
+                t = np.asarray(model.get_score_tables(None), dtype=np.float64)
+                eng = cls(model.U, t, device=device, dtype=dtype, exact_generic=exact_generic)
             cache[key] = eng
         return eng
 
@@ -304,7 +333,8 @@ class Engine:
         from .limits import exact_limits
         return exact_limits(self.S, self.E, self.factored, cap, host_blas_arch(),
                             exact_option=bool(self.get_option("exact")),
-                            exact_generic=bool(self.get_option("exact_generic")))
+                            exact_generic=bool(self.get_option("exact_generic")),
+                            row_shared=bool(self.get_option("exact_shared")))
 
     def exact_status(self, cap: int = 0):
         """(True, "") when the fused step and the sampler's score calls run in

@@ -74,13 +74,27 @@ class Limit:
 
 
 def exact_limits(S: int, E: int, factored: bool, cap: int = 0, host_blas: str | None = "SkylakeX",
-                 exact_option: bool = True, *, exact_generic: bool = False) -> list[Limit]:
+                 exact_option: bool = True, *, exact_generic: bool = False, row_shared: bool = False) -> list[Limit]:
     """The exact path's limits for a model of S S-genes and E effects.
     ``exact_generic``: the engine's option of that name (set before staging)
-    -- a generic, real-valued table is covered too within its bounds."""
+    -- a generic, real-valued table is covered too within its bounds.
+    ``row_shared`` (with ``exact_generic``): the generic table shares parent
+    j's row among all children (``TableModel.from_log_ratios``, the engine's
+    ``exact_shared``) -- covered over the factored model's range of E."""
     leaves = pairwise_leaves(E)
     parts = pairwise_parts(E)
-    if exact_generic:
+    if exact_generic and row_shared:
+        table_form = Limit(
+            "table form", "factored: every off-diagonal row T[.][j] shared by all children, two-valued (every "
+            f"table nem.py builds); or, with option exact_generic, a real-valued table with max|T|, max|U| <= "
+            f"{MAX_ABS_EXACT_GENERIC:g} and either the row T[.][j] shared by all children (per-effect log ratios; "
+            f"E <= {MAX_PARTS * NUMPY_BUFSIZE}, {MAX_PARTS} numpy buffers) or E <= {MAX_E_EXACT_GENERIC} (one "
+            "numpy buffer)",
+            "factored" if factored else f"generic, rows shared, E={E}", bool(factored) or parts is not None,
+            f"ExactArithmeticWarning (strict=True: RuntimeError); the fast kernels -- a row-shared table with E > "
+            f"{MAX_PARTS * NUMPY_BUFSIZE} or max|T|, max|U| > {MAX_ABS_EXACT_GENERIC:g} (Engine.exact_status reads "
+            "the library's verdict on the staged values)", False)
+    elif exact_generic:
         table_form = Limit(
             "table form", "factored: every off-diagonal row T[.][j] shared by all children, two-valued (every "
             f"table nem.py builds); or, with option exact_generic, any real-valued table with E <= "

@@ -75,15 +75,21 @@ class TableModel:
     place of a ``NEM``: it has the attributes they read (``num_s``, ``num_e``,
     ``U``, ``get_score_tables``) and no knockdown matrix, so its engine is
     staged from the tables (``Engine.for_model``, option ``exact_generic``:
-    the reference's bits for E <= 8192 and max|T|, max|U| <= 700).
+    the reference's bits for max|T|, max|U| <= 700 and E <= 8192, or E <=
+    524288 for a model of log ratios).
 
     A sampler built on a ``TableModel`` without an ``engine=`` always takes
-    that option, and with it the exact step's stored rows (chains x pairs x
-    plan doubles of device memory: 0.56 GB at 64 x 2000, 16 chains).  To run
-    the model without it, stage ``Engine(U, T)`` yourself and pass it as
+    that option.  A table with its own rows per child then runs the exact
+    step on stored rows (chains x pairs x plan doubles of device memory: 0.56
+    GB at 64 x 2000, 16 chains).  A model of log ratios (``from_log_ratios``)
+    is staged from ``R`` alone -- ``T`` is built only when read
+    (``tables_built``) -- and runs on per-parent recompute rows (chains x S x
+    plan doubles: 18 MB at 64 x 2000, 16 chains, plus 1 MB per staged table).  To run
+    a model without the option, stage ``Engine(U, T)`` yourself and pass it as
     ``engine=``."""
 
     observed_knockdown_mat = None
+    R = None   # from_log_ratios: the log ratios (S, E) the model was made from
 
     def __init__(self, U, T):
         T = np.ascontiguousarray(T, dtype=np.float64)
@@ -93,7 +99,23 @@ class TableModel:
         if U.shape != (T.shape[0] + 1, T.shape[2]):
             raise ValueError(f"U must be ({T.shape[0] + 1}, {T.shape[2]}), got {U.shape}")
         self.num_s, self.num_e = int(T.shape[0]), int(T.shape[2])
-        self.U, self.T = U, T
+        self.U, self._T = U, T
+
+    @property
+    def T(self) -> np.ndarray:
+        """The score tables (S, S, E); a model of log ratios builds them on
+        first access (the same array from then on)."""
+        if self._T is None:
+            s, e = self.R.shape
+            t = np.empty((s, s, e), dtype=np.float64)
+            t[:] = self.R[None, :, :]
+            self._T = t
+        return self._T
+
+    @property
+    def tables_built(self) -> bool:
+        """True once ``T`` exists on the host."""
+        return self._T is not None
 
     @classmethod
     def from_log_ratios(cls, R) -> "TableModel":
@@ -106,9 +128,10 @@ class TableModel:
         if R.ndim != 2:
             raise ValueError(f"R must be (S, E), got {R.shape}")
         s, e = R.shape
-        T = np.empty((s, s, e), dtype=np.float64)
-        T[:] = R[None, :, :]
-        return cls(np.vstack([R, np.zeros((1, e))]), T)
+        self = cls.__new__(cls)
+        self.num_s, self.num_e = int(s), int(e)
+        self.R, self.U, self._T = R, np.vstack([R, np.zeros((1, e))]), None
+        return self
 
     def get_score_tables(self, _knockdown_mat=None):
         """The tables themselves (the same array on every call)."""

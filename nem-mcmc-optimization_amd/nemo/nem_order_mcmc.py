@@ -104,7 +104,10 @@ class NEMOrderMCMC:
         self.U = nem.U.copy()
         self.perm_orders = [perm_order]
         self.parent_weights = np.zeros((self.num_s, self.num_s))
-        self.score_tables = nem.get_score_tables(nem.observed_knockdown_mat)
+        # (a model that holds its log ratios builds its S*S*E tables only if
+        # someone asks for them: the engine is staged from R)
+        self._score_tables = (None if getattr(nem, "R", None) is not None
+                              else nem.get_score_tables(nem.observed_knockdown_mat))
         self.cap = int(cap)
         self.engine = engine if engine is not None else Engine.for_nem(nem, device=device, dtype=dtype)
         if self.engine.get_option("exact"):
@@ -116,7 +119,7 @@ class NEMOrderMCMC:
                     raise RuntimeError(msg)
                 warnings.warn(msg, ExactArithmeticWarning, stacklevel=2)
         self.get_permissible_parents(perm_order, init=True, init_value=1.0)
-        self.cell_ratios = self.compute_cell_ratios(self.parent_weights, self.score_tables)
+        self.cell_ratios = self.compute_cell_ratios(self.parent_weights, None)
         self.perm_order = perm_order
         self.I = np.identity(self.num_s)
         self._eval1 = None      # (pos, W~ or None, W) of the last eval #1
@@ -200,9 +203,22 @@ class NEMOrderMCMC:
         return pos
 
     # -- A4 + A5 -----------------------------------------------------------------
+    @property
+    def score_tables(self):
+        """The model's score tables (nem_order_mcmc.py:44), built on first
+        access for a model staged from its log ratios."""
+        if self._score_tables is None:
+            self._score_tables = self.nem.get_score_tables(self.nem.observed_knockdown_mat)
+        return self._score_tables
+
+    @score_tables.setter
+    def score_tables(self, value):
+        self._score_tables = value
+
     def compute_cell_ratios(self, weights, score_tables):
         """Reference: nem_order_mcmc.py:79-87 (expit applied to the weights
-        of the permissible parents).  Evaluated by the score kernel."""
+        of the permissible parents).  Evaluated by the score kernel
+        (``score_tables`` None: the sampler's own tables)."""
         eng = self._engine_for(score_tables)
         w01 = expit(np.asarray(weights, dtype=np.float64))
         out = eng.score(self._pos[None, :], w01[None], cap=self.cap, want_cells=True)
@@ -215,7 +231,7 @@ class NEMOrderMCMC:
         return ow, ll
 
     def _engine_for(self, score_tables):
-        if score_tables is self.score_tables:
+        if score_tables is None or score_tables is self.score_tables:
             return self.engine
         t = np.asarray(score_tables, dtype=np.float64)
         return Engine(self.U, t, device=self.engine.device, dtype=self.engine.dtype)
@@ -359,7 +375,8 @@ class NEMOrderMCMC:
         """Reference: nem_order_mcmc.py:160-170.  The c vector is assembled on
         the host from the staged inputs; the L-BFGS-B solve runs on the GPU."""
         ow = self.order_weights
-        lv = np.exp(self.score_tables[i][k])
+        r = getattr(self.nem, "R", None)   # (a log-ratio model: T[i][k] = R[k])
+        lv = np.exp(self.score_tables[i][k] if r is None or self._score_tables is not None else r[k])
         a = (lv - 1.0) * ow[k]
         s = expit(self.parent_weights[i][k])
         b = 1.0 - s * a + s * (lv - 1.0)

@@ -3,6 +3,7 @@ the fast generic step and the factored exact step of the same build.
 
     python tools/generic_step_probe.py --mode generic_exact|generic_fast|factored_exact
                                        [--chains 16] [--steps 20] [--warmup 3] [--s 64] [--e 2000]
+                                       [--form F] [--cform 0|1]
     python tools/generic_step_probe.py --summarize KERNEL_STATS.csv --steps N
 
 generic_*: ``TableModel.from_log_ratios(R)``, R ~ N(0, 1) (seed 0), with option
@@ -12,6 +13,15 @@ chains (random orders, W ~ U(-3, 3)) and prints the wall milliseconds per
 step.  Under ``rocprofv3 --kernel-trace --stats`` the run's kernel_stats.csv
 holds the kernels of all warmup + steps calls; ``--summarize`` prints the
 kernel milliseconds per step and each kernel's share from it.
+
+``--form`` / ``--cform`` set the exact local optima's ``exact_form`` and
+``exact_cform`` (a row-shared generic table follows them like a factored one:
+``--cform 0`` stored rows, ``1`` per-parent recompute rows; ``--form 2``
+throughput, ``7`` slot, ...).  The result line also names the form that ran
+(``exact_form_used``), ``exact_rc`` / ``exact_shared``, and the device memory
+taken between staging and the end of the first step (``step_mem_mb``: the
+buffers ``exact_reserve`` and ``nemo_reserve`` allocate), from
+``torch.cuda.mem_get_info`` when torch is importable.
 """
 import argparse
 import csv
@@ -46,6 +56,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--s", type=int, default=64)
     ap.add_argument("--e", type=int, default=2000)
+    ap.add_argument("--form", type=int, default=None)
+    ap.add_argument("--cform", type=int, default=None)
     ap.add_argument("--summarize")
     a = ap.parse_args()
     if a.summarize:
@@ -68,6 +80,26 @@ def main():
     exact = bool(eng.get_option("exact")) and bool(eng.get_option("exact_ok"))
     if exact != (a.mode != "generic_fast"):
         raise SystemExit(f"{a.mode}: exact={eng.get_option('exact')} exact_ok={eng.get_option('exact_ok')}")
+    if a.form is not None:
+        eng.set_option("exact_form", a.form)
+    if a.cform is not None:
+        eng.set_option("exact_cform", a.cform)
+
+    def used_mb():
+        try:
+            import torch
+            free, total = torch.cuda.mem_get_info(eng.device)
+            return (total - free) / 2**20
+        except Exception:
+            return None
+
+    def opt(name):   # (None on a build without the option: the probe also times older builds)
+        try:
+            return eng.get_option(name)
+        except Exception:
+            return None
+
+    mem0 = used_mb()
     rng = np.random.default_rng(3)
     pos = np.array([rng.permutation(s) for _ in range(n)], dtype=np.int32)
     w = rng.uniform(-3, 3, (n, s, s))
@@ -77,8 +109,10 @@ def main():
     def step():
         return eng.optimal_weights(pos, w01, anc, w, SIG0, SIG1, raise_on_fail=False)
 
+    mem1 = None
     for _ in range(a.warmup):
         step()
+        mem1 = used_mb() if mem1 is None else mem1
     ts = []
     for _ in range(a.steps):
         t0 = time.perf_counter()
@@ -86,6 +120,10 @@ def main():
         ts.append(time.perf_counter() - t0)
     print(json.dumps({"mode": a.mode, "S": s, "E": e, "chains": n, "steps": a.steps, "warmup": a.warmup,
                       "factored": eng.factored, "exact_form": eng.get_option("exact_form"),
+                      "exact_cform": eng.get_option("exact_cform"),
+                      "exact_form_used": opt("exact_form_used"), "exact_rc": opt("exact_rc"),
+                      "exact_shared": opt("exact_shared"),
+                      "step_mem_mb": None if mem0 is None or mem1 is None else mem1 - mem0,
                       "wall_ms_per_step_median": 1e3 * float(np.median(ts)),
                       "wall_ms_per_step_mean": 1e3 * float(np.mean(ts)),
                       "ll1_0": float(out[1][0]), "ll_dag_0": float(out[2][0])}))
