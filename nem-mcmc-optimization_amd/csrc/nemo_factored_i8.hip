@@ -40,6 +40,20 @@
 #ifndef NEMO_I8L_RINIT
 #define NEMO_I8L_RINIT 1
 #endif
+// that C-init (T_0 & 511) 2^7 as one 16-bit shift (1) or as a mask and a
+// 32-bit shift (0): the same integer
+#ifndef NEMO_I8L_CINIT16
+#define NEMO_I8L_CINIT16 1
+#endif
+// score_i8l_kernel's two-tile walk, the B-fragment prefetch: two register
+// sets swapping roles over two iterations per trip (1) or one set copied at
+// the loop top (0: 8 v_mov_b64 per iteration; the same bits).  The persistent
+// kernel (score_i8p_kernel) keeps the one-set form: its walk shares the
+// registers with the next evaluation's prep and the second copy of the loop
+// body spills.
+#ifndef NEMO_I8L_PINGPONG
+#define NEMO_I8L_PINGPONG 1
+#endif
 // register budget: waves per SIMD the int8 score kernel is compiled for
 #ifndef NEMO_I8_WAVES_PER_SIMD
 #define NEMO_I8_WAVES_PER_SIMD 2
@@ -240,6 +254,11 @@ __device__ __forceinline__ void i8o_digits(int8_t* A8, int i, int j, double d, i
 // [-128, 127]) in slices 0-3, and l = rint((v - h) 2^18) (|l| <= 2^17) as
 // three balanced base-64 digits in slices 4-6, so T_0 counts units of 2^-20
 // and T_1 units of 2^-38 of y = x / ln 2 (per-entry error <= 2^-39).
+// Slice 4 holds its digit (in [-32, 32]) DOUBLED: its accumulator is then
+// 2 l_0 and every walk forms T_1 = acc_4 2^11 + l_1, the same integer as
+// l_0 2^12 + l_1.  The spare factor lets the two-tile walk put the
+// remainder's upper part into that accumulator's C-init with one 16-bit
+// shift (i8l_cinit16).
 constexpr double kL2Scale = 1512775.3951951857;   // 2^20 / ln 2
 
 template <int SPAD, int ROWC>
@@ -254,7 +273,7 @@ __device__ __forceinline__ void i8l_digits(int8_t* A8, int i, int j, double d) {
   A8[1 * SL + off] = (int8_t)(((hb >> 12) & 63) - 32);
   A8[2 * SL + off] = (int8_t)(((hb >> 6) & 63) - 32);
   A8[3 * SL + off] = (int8_t)((hb & 63) - 32);
-  A8[4 * SL + off] = (int8_t)(lb >> 12);
+  A8[4 * SL + off] = (int8_t)(2 * (lb >> 12));  // doubled (see above): [-64, 64]
   A8[5 * SL + off] = (int8_t)(((lb >> 6) & 63) - 32);
   A8[6 * SL + off] = (int8_t)((lb & 63) - 32);
 }
@@ -719,6 +738,20 @@ __device__ __forceinline__ double exp2_fx_series_r(int rr) {
   const double r = (double)rr;
   return fma(r, fma(r, kL2C2, kL2C1), kL2C0);
 }
+// slice 4's C-init in the two-tile walk: (T_0 & 511) 2^7 (the remainder's
+// upper part against the doubled slice-4 digit, see i8l_digits).  A 16-bit
+// left shift by 7 keeps exactly bits 0-8 of T_0, at bits 7-15, and on gfx9 a
+// 16-bit VALU result is written with the destination's high half zeroed: one
+// instruction where the 32-bit form needs a mask and a shift.
+__device__ __forceinline__ int i8l_cinit16(uint32_t t0) {
+#if NEMO_I8L_CINIT16
+  int r;
+  asm("v_lshlrev_b16 %0, 7, %1" : "=v"(r) : "v"(t0));
+  return r;
+#else
+  return (int)((t0 & 511u) << 7);
+#endif
+}
 __device__ __forceinline__ double exp2_fx_apply(uint32_t t0, uint64_t ev, double p, double acc) {
   // (one v_bitop3: bits 9-19 of T_0 cancel the index the entry carries)
   const uint32_t hi = (t0 & ~511u) ^ (uint32_t)(ev >> 32);
@@ -921,7 +954,7 @@ hipError_t launch_i8o_t(Ctx& c, int batch, int cap, const int32_t* d_pos, const 
 // hook(it) runs between iterations it and it + 1 (it = 0, 1, ...) and returns
 // nothing the walk reads: score_i8p_kernel runs the next evaluation's digit
 // prep there.  Returns the number of iterations walked.
-template <int NR, int WAVES, class Hook>
+template <int NR, int WAVES, bool PP, class Hook>
 __device__ __forceinline__ int i8l_walk2(const i32x4* __restrict__ Al0, const i32x4* __restrict__ Gi,
                                         const i32x4* __restrict__ Bt, const i32x4* __restrict__ Bt64,
                                         int set, int s_end, int ntiles, int E, int col, int lane,
@@ -949,7 +982,10 @@ __device__ __forceinline__ int i8l_walk2(const i32x4* __restrict__ Al0, const i3
     };
     i32x4 bca = bload(t, 0), bca64 = bload(t, 1);
     i32x4 bcb = bload(t2, 0), bcb64 = bload(t2, 1);
-    for (;;) {
+    // one iteration on the fragments (b1a, b64a, b1b, b64b), prefetching the
+    // next iteration's into (na, na64, nb, nb64); false after the last
+    auto iter = [&](const i32x4 b1a, const i32x4 b64a, const i32x4 b1b, const i32x4 b64b, i32x4& na,
+                    i32x4& na64, i32x4& nb, i32x4& nb64) -> bool {
       uint32_t ao = a_lane;
       asm volatile("" : "+v"(ao));
       const i32x4* Al = Al0 + ao;
@@ -962,11 +998,10 @@ __device__ __forceinline__ int i8l_walk2(const i32x4* __restrict__ Al0, const i3
       const bool more = setn < s_end;
       const int tla = __builtin_amdgcn_readfirstlane(more ? tn : t);
       const int tlb = __builtin_amdgcn_readfirstlane(more ? (tn + 1 < tend(setn) ? tn + 1 : tn) : t);
-      const i32x4 b1a = bca, b64a = bca64, b1b = bcb, b64b = bcb64;
-      bca = bload(tla, 0);
-      bca64 = bload(tla, 1);
-      bcb = bload(tlb, 0);
-      bcb64 = bload(tlb, 1);
+      na = bload(tla, 0);
+      na64 = bload(tla, 1);
+      nb = bload(tlb, 0);
+      nb64 = bload(tlb, 1);
       double la0 = 0.0, la1 = 0.0, lb0 = 0.0, lb1 = 0.0;
 #pragma unroll
       for (int r = 0; r < NR; ++r) {
@@ -997,9 +1032,10 @@ __device__ __forceinline__ int i8l_walk2(const i32x4* __restrict__ Al0, const i3
         }
 #if NEMO_I8L_RINIT
         // slices 5-6 first; then T_0 of both tiles and their table reads, and
-        // the remainder's upper part (T_0 & 511) 2^6 becomes the C-init of
-        // slice 4, so R = l0 2^12 + l1 is one shift-add (the same integer R
-        // as exp2_fx_series forms, so the same bits; one VOP3 less per cell)
+        // the remainder's upper part (T_0 & 511) 2^7 becomes the C-init of
+        // slice 4 (doubled digits: i8l_digits), so R = l0 2^11 + l1 is one
+        // shift-add (the same integer R as exp2_fx_series forms, so the same
+        // bits; one VOP3 less per cell, and the C-init itself is one VOP2)
         {
           const i32x4 a = A(5);
           l1a = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, b64a, c1, 0, 0, 0);
@@ -1017,13 +1053,13 @@ __device__ __forceinline__ int i8l_walk2(const i32x4* __restrict__ Al0, const i3
         for (int g = 0; g < 4; ++g) {
           t0a[g] = ((uint32_t)h0a[g] << 12) + (uint32_t)h1a[g];
           eva[g] = exp2_fx_load(t0a[g]);
-          ma[g] = (int)((t0a[g] & 511u) << 6);
+          ma[g] = i8l_cinit16(t0a[g]);
         }
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
           t0b[g] = ((uint32_t)h0b[g] << 12) + (uint32_t)h1b[g];
           evb[g] = exp2_fx_load(t0b[g]);
-          mb[g] = (int)((t0b[g] & 511u) << 6);
+          mb[g] = i8l_cinit16(t0b[g]);
         }
         {
           const i32x4 a = A(4);
@@ -1034,7 +1070,7 @@ __device__ __forceinline__ int i8l_walk2(const i32x4* __restrict__ Al0, const i3
                        double& ls0, double& ls1) {
           double pr[4];
 #pragma unroll
-          for (int g = 0; g < 4; ++g) pr[g] = exp2_fx_series_r((int)(((uint32_t)l0[g] << 12) + (uint32_t)l1[g]));
+          for (int g = 0; g < 4; ++g) pr[g] = exp2_fx_series_r((int)(((uint32_t)l0[g] << 11) + (uint32_t)l1[g]));
 #pragma unroll
           for (int g = 0; g < 4; ++g) {
             if (g & 1) ls1 = exp2_fx_apply(t0[g], evv[g], pr[g], ls1);
@@ -1071,7 +1107,7 @@ __device__ __forceinline__ int i8l_walk2(const i32x4* __restrict__ Al0, const i3
           }
 #pragma unroll
           for (int g = 0; g < 4; ++g)
-            pr[g] = exp2_fx_series(t0[g], (int)(((uint32_t)l0[g] << 12) + (uint32_t)l1[g]));
+            pr[g] = exp2_fx_series(t0[g], (int)(((uint32_t)l0[g] << 11) + (uint32_t)l1[g]));
 #pragma unroll
           for (int g = 0; g < 4; ++g) {
             if (g & 1) ls1 = exp2_fx_apply(t0[g], evv[g], pr[g], ls1);
@@ -1103,10 +1139,30 @@ __device__ __forceinline__ int i8l_walk2(const i32x4* __restrict__ Al0, const i3
         lexp = 0;
       }
       hook(it++);
-      if (!more) break;
+      if (!more) return false;
       t = tn;
       t2 = tlb;
       set = setn;
+      return true;
+    };
+    if constexpr (PP) {
+      // two iterations per trip, the two fragment sets swapping roles: no
+      // register copies of the prefetched fragments at the loop top
+      i32x4 bqa, bqa64, bqb, bqb64;
+      for (;;) {
+        if (!iter(bca, bca64, bcb, bcb64, bqa, bqa64, bqb, bqb64)) break;
+        if (!iter(bqa, bqa64, bqb, bqb64, bca, bca64, bcb, bcb64)) break;
+      }
+    } else {
+      for (;;) {
+        i32x4 na, na64, nb, nb64;
+        const bool more = iter(bca, bca64, bcb, bcb64, na, na64, nb, nb64);
+        bca = na;
+        bca64 = na64;
+        bcb = nb;
+        bcb64 = nb64;
+        if (!more) break;
+      }
     }
   }
   return it;
@@ -1119,8 +1175,9 @@ __device__ __forceinline__ int i8l_walk2(const i32x4* __restrict__ Al0, const i3
 // y = x / ln 2 in fixed point and 2^y = e^x is assembled from the integer
 // accumulators (exp2_fx_acc).  T_0 = acc_0 2^12 + acc_1 (slices 0-3, units
 // 2^-20, G's high part and the exponent bias 1023 << 20 in acc_1's C-init);
-// T_1 = acc_2 2^12 + acc_3 (slice 4; slices 5-6 with G's low part as C-init,
-// units 2^-38): 7 MFMAs per row block against 8.  Requires the diagonal form
+// T_1 = acc_2 2^11 + acc_3 (slice 4, its digits doubled: i8l_digits; slices
+// 5-6 with G's low part as C-init, units 2^-38): 7 MFMAs per row block
+// against 8.  Requires the diagonal form
 // (stage_i8o).
 // ---------------------------------------------------------------------------
 // MODE (fact_kernel 20, an experiment): 0 = prep and walk in one block (the
@@ -1185,7 +1242,8 @@ __global__ __launch_bounds__(WAVES * kWave, OCC) void score_i8l_kernel(
     int8_t* A8 = (int8_t*)ev.A;
     for (int k = tid; k < S * NSL; k += blockDim.x) {
       const int i = k / NSL, sl = k - i * NSL;
-      A8[sl * SPAD * 64 + a_byte<4>(i, i)] = udig[i * 8 + sl];
+      const int8_t d = udig[i * 8 + sl];
+      A8[sl * SPAD * 64 + a_byte<4>(i, i)] = sl == 4 ? (int8_t)(2 * d) : d;  // slice 4 doubled (i8l_digits)
     }
   }
   {
@@ -1282,7 +1340,7 @@ __global__ __launch_bounds__(WAVES * kWave, OCC) void score_i8l_kernel(
           }
   #pragma unroll
           for (int g = 0; g < 4; ++g)
-            pr[g] = exp2_fx_series(t0[g], (int)(((uint32_t)l0[g] << 12) + (uint32_t)l1[g]));
+            pr[g] = exp2_fx_series(t0[g], (int)(((uint32_t)l0[g] << 11) + (uint32_t)l1[g]));
   #pragma unroll
           for (int g = 0; g < 4; ++g) {
             if (g & 1) ls1 = exp2_fx_apply(t0[g], ev[g], pr[g], ls1);
@@ -1313,7 +1371,7 @@ __global__ __launch_bounds__(WAVES * kWave, OCC) void score_i8l_kernel(
     // arithmetic per cell and the same order of the column products as TT = 1,
     // so the same bits.  The second tile of a set's odd tail repeats the first
     // and is not multiplied in.
-    i8l_walk2<NR, WAVES>(ev.A, Gi, Bt, Bt64, set, s_end, ntiles, E, col, lane, a_lane, nullsum, partial, b,
+    i8l_walk2<NR, WAVES, NEMO_I8L_PINGPONG != 0>(ev.A, Gi, Bt, Bt64, set, s_end, ntiles, E, col, lane, a_lane, nullsum, partial, b,
                          nsets, ltab, [](int) {});
   }
   if (split == 1) {
@@ -1393,7 +1451,8 @@ __global__ __launch_bounds__(8 * kWave, NEMO_I8O_WAVES_PER_SIMD) void score_i8s_
     int8_t* A8 = (int8_t*)ev.A;
     for (int k = tid; k < S * NSL; k += blockDim.x) {
       const int i = k / NSL, sl = k - i * NSL;
-      A8[sl * SPAD * 64 + a_byte<4>(i, i)] = udig[i * 8 + sl];
+      const int8_t d = udig[i * 8 + sl];
+      A8[sl * SPAD * 64 + a_byte<4>(i, i)] = sl == 4 ? (int8_t)(2 * d) : d;  // slice 4 doubled (i8l_digits)
     }
   }
   {
@@ -1459,7 +1518,7 @@ __global__ __launch_bounds__(8 * kWave, NEMO_I8O_WAVES_PER_SIMD) void score_i8s_
         }
 #pragma unroll
         for (int g = 0; g < 4; ++g)
-          pr[g] = exp2_fx_series(t0[g], (int)(((uint32_t)l0[g] << 12) + (uint32_t)l1[g]));
+          pr[g] = exp2_fx_series(t0[g], (int)(((uint32_t)l0[g] << 11) + (uint32_t)l1[g]));
         double ls0 = 0.0, ls1 = 0.0;
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
@@ -1567,7 +1626,8 @@ __global__ __launch_bounds__(WAVES * kWave, NEMO_I8L2_OCC) void score_i8p_kernel
     int8_t* A8 = (int8_t*)evb(k).A;
     for (int q = tid; q < S * NSL; q += blockDim.x) {
       const int i = q / NSL, sl = q - i * NSL;
-      A8[sl * SPAD * 64 + a_byte<4>(i, i)] = udig[i * 8 + sl];
+      const int8_t d = udig[i * 8 + sl];
+      A8[sl * SPAD * 64 + a_byte<4>(i, i)] = sl == 4 ? (int8_t)(2 * d) : d;  // slice 4 doubled (i8l_digits)
     }
   };
   auto prep = [&](int k, int e) {  // this wave's passes of evaluation e into buffer k
@@ -1620,7 +1680,7 @@ __global__ __launch_bounds__(WAVES * kWave, NEMO_I8L2_OCC) void score_i8p_kernel
   for (int e = b0; e < batch; e += nb, k ^= 1) {
     const int en = e + nb;
     bool pending = en < batch;
-    i8l_walk2<NR, WAVES>(evb(k).A, (const i32x4*)gib(k), Bt, Bt64, w, nsets, ntiles, E, col, lane, a_lane,
+    i8l_walk2<NR, WAVES, false>(evb(k).A, (const i32x4*)gib(k), Bt, Bt64, w, nsets, ntiles, E, col, lane, a_lane,
                          nullsum, partial, (size_t)e, nsets, ltab, [&](int it) {
                            if (pending && it == 0) {
                              prep(k ^ 1, en);
@@ -1754,7 +1814,7 @@ __device__ __forceinline__ void i8w_digits(int8_t* A8, int i, int j, double d) {
   A8[(1 * kWideKH) * SL + off] = (int8_t)(((hb >> 12) & 63) - 32);
   A8[(2 * kWideKH) * SL + off] = (int8_t)(((hb >> 6) & 63) - 32);
   A8[(3 * kWideKH) * SL + off] = (int8_t)((hb & 63) - 32);
-  A8[(4 * kWideKH) * SL + off] = (int8_t)(lb >> 12);
+  A8[(4 * kWideKH) * SL + off] = (int8_t)(2 * (lb >> 12));  // doubled, as i8l_digits
   A8[(5 * kWideKH) * SL + off] = (int8_t)(((lb >> 6) & 63) - 32);
   A8[(6 * kWideKH) * SL + off] = (int8_t)((lb & 63) - 32);
 }
@@ -1862,7 +1922,8 @@ __global__ __launch_bounds__(WAVES * kWave, OCC) void score_i8w_kernel(
     int8_t* A8 = (int8_t*)ev.A;
     for (int k = tid; k < S * NSL; k += blockDim.x) {
       const int i = k / NSL, sl = k - i * NSL;
-      A8[(sl * kWideKH + (i >> 6)) * SPAD * 64 + a_byte<4>(i, i & 63)] = udig[i * 8 + sl];
+      const int8_t d = udig[i * 8 + sl];
+      A8[(sl * kWideKH + (i >> 6)) * SPAD * 64 + a_byte<4>(i, i & 63)] = sl == 4 ? (int8_t)(2 * d) : d;
     }
   }
   {
@@ -1897,7 +1958,9 @@ __global__ __launch_bounds__(WAVES * kWave, OCC) void score_i8w_kernel(
     // for both (half the LDS A traffic); rowsum_pair leaves tile a's column
     // sums in rows 0 / 2 and tile b's in rows 1 / 3 (as score_i8l_kernel's
     // two-tile walk).  A set of one tile (odd ntiles) repeats it and does not
-    // multiply the copy in.
+    // multiply the copy in.  Slices 5-6 run before slice 4, whose C-init is
+    // the remainder's upper part (i8l_cinit16), as in i8l_walk2: R costs one
+    // shift and one shift-add per cell instead of a mask and two shift-adds.
     for (int set = w; set < nsets; set += WAVES) {
       const int ta = kWideSetT * set;
       const bool two = ta + 1 < ntiles;
@@ -1914,7 +1977,7 @@ __global__ __launch_bounds__(WAVES * kWave, OCC) void score_i8w_kernel(
         const i32x4 c1 = Gi[(SPAD + 16 * r) / 4 + rg];
         auto A = [&](int sl, int h) { return Al[((sl * kWideKH + h) * SPAD + 16 * r) * 4]; };
         i32x4 h0a = i32x4{0, 0, 0, 0}, h0b = i32x4{0, 0, 0, 0}, h1a = c0, h1b = c0;
-        i32x4 l0a = i32x4{0, 0, 0, 0}, l0b = i32x4{0, 0, 0, 0}, l1a = c1, l1b = c1;
+        i32x4 l1a = c1, l1b = c1;
 #pragma unroll
         for (int h = 0; h < kWideKH; ++h) {
           {
@@ -1938,11 +2001,6 @@ __global__ __launch_bounds__(WAVES * kWave, OCC) void score_i8w_kernel(
             h1b = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, b1b[h], h1b, 0, 0, 0);
           }
           {
-            const i32x4 a = A(4, h);
-            l0a = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, b1a[h], l0a, 0, 0, 0);
-            l0b = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, b1b[h], l0b, 0, 0, 0);
-          }
-          {
             const i32x4 a = A(5, h);
             l1a = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, b64a[h], l1a, 0, 0, 0);
             l1b = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, b64b[h], l1b, 0, 0, 0);
@@ -1953,27 +2011,42 @@ __global__ __launch_bounds__(WAVES * kWave, OCC) void score_i8w_kernel(
             l1b = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, b1b[h], l1b, 0, 0, 0);
           }
         }
-        auto epi = [&](const i32x4 h0, const i32x4 h1, const i32x4 l0, const i32x4 l1, double& ls0,
-                       double& ls1) {
-          uint32_t t0[4];
-          uint64_t evv[4];
+        // T_0 of both tiles and their table reads, then slice 4 from the
+        // C-init (T_0 & 511) 2^7 (i8l_walk2's order): R = l0 2^11 + l1
+        uint32_t t0a[4], t0b[4];
+        uint64_t eva[4], evb[4];
+        i32x4 l0a, l0b;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          t0a[g] = ((uint32_t)h0a[g] << 12) + (uint32_t)h1a[g];
+          eva[g] = exp2_fx_load(t0a[g]);
+          l0a[g] = i8l_cinit16(t0a[g]);
+        }
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          t0b[g] = ((uint32_t)h0b[g] << 12) + (uint32_t)h1b[g];
+          evb[g] = exp2_fx_load(t0b[g]);
+          l0b[g] = i8l_cinit16(t0b[g]);
+        }
+#pragma unroll
+        for (int h = 0; h < kWideKH; ++h) {
+          const i32x4 a = A(4, h);
+          l0a = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, b1a[h], l0a, 0, 0, 0);
+          l0b = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, b1b[h], l0b, 0, 0, 0);
+        }
+        auto epi = [&](const uint32_t (&t0)[4], const uint64_t (&evv)[4], const i32x4 l0, const i32x4 l1,
+                       double& ls0, double& ls1) {
           double pr[4];
 #pragma unroll
-          for (int g = 0; g < 4; ++g) {
-            t0[g] = ((uint32_t)h0[g] << 12) + (uint32_t)h1[g];
-            evv[g] = exp2_fx_load(t0[g]);
-          }
-#pragma unroll
-          for (int g = 0; g < 4; ++g)
-            pr[g] = exp2_fx_series(t0[g], (int)(((uint32_t)l0[g] << 12) + (uint32_t)l1[g]));
+          for (int g = 0; g < 4; ++g) pr[g] = exp2_fx_series_r((int)(((uint32_t)l0[g] << 11) + (uint32_t)l1[g]));
 #pragma unroll
           for (int g = 0; g < 4; ++g) {
             if (g & 1) ls1 = exp2_fx_apply(t0[g], evv[g], pr[g], ls1);
             else ls0 = exp2_fx_apply(t0[g], evv[g], pr[g], ls0);
           }
         };
-        epi(h0a, h1a, l0a, l1a, la0, la1);
-        epi(h0b, h1b, l0b, l1b, lb0, lb1);
+        epi(t0a, eva, l0a, l1a, la0, la1);
+        epi(t0b, evb, l0b, l1b, lb0, lb1);
       }
       const double l = rowsum_pair(la0 + la1, lb0 + lb1) + 1.0;  // + e^0 of the null row
       const bool tile_b = (lane & 16) != 0;
@@ -2026,7 +2099,7 @@ __global__ __launch_bounds__(WAVES * kWave, OCC) void score_i8w_kernel(
           }
   #pragma unroll
           for (int g = 0; g < 4; ++g)
-            pr[g] = exp2_fx_series(t0[g], (int)(((uint32_t)l0[g] << 12) + (uint32_t)l1[g]));
+            pr[g] = exp2_fx_series(t0[g], (int)(((uint32_t)l0[g] << 11) + (uint32_t)l1[g]));
   #pragma unroll
           for (int g = 0; g < 4; ++g) {
             if (g & 1) ls1 = exp2_fx_apply(t0[g], evv[g], pr[g], ls1);
