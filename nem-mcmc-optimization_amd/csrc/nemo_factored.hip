@@ -122,8 +122,11 @@ __device__ __forceinline__ void delta_row(int S, int SPAD, int cap, int b, int q
     if (ok) {
       const int j = perm[p];
       const double s = wrow[j];
-      const double lo = log(fma(s, e_lo[j] - 1.0, 1.0));
-      const double hi = log(fma(s, e_hi[j] - 1.0, 1.0));
+      // 1 - s + s e^t with 1 - s formed first (exact for s >= 0.5): fma(s, e^t - 1, 1)
+      // rounds e^t - 1 to 2^-53, which is all of a small e^t once s reaches 1
+      const double s1 = 1.0 - s;
+      const double lo = log(fma(s, e_lo[j], s1));
+      const double hi = log(fma(s, e_hi[j], s1));
       d = hi - lo;
       glo = lo;
     }

@@ -187,8 +187,9 @@ __device__ __forceinline__ void i8_prep_passes(EvalLds e, int k0, int w, int lan
     double lo = 0.0;
     if (act && !(NEMO_I8_ABLATE & 8)) {  // (8: instrumented build, no digits)
       const int i = ii[kk], j = jj[kk];
-      lo = log_fast(fma(sw[kk], elo_s[j] - 1.0, 1.0), ltab);
-      const double d = log_fast(fma(sw[kk], ehi_s[j] - 1.0, 1.0), ltab) - lo;
+      const double s1 = 1.0 - sw[kk];  // (1 - s first: delta_row, nemo_factored.hip)
+      lo = log_fast(fma(sw[kk], elo_s[j], s1), ltab);
+      const double d = log_fast(fma(sw[kk], ehi_s[j], s1), ltab) - lo;
       // fixed point: x = Delta * 2^(6-c) in [-32, 32]; every step is exact
       double x = ldexp(d, 6 - cexp);
 #pragma unroll
@@ -335,8 +336,9 @@ __device__ __forceinline__ void i8o_prep_passes(EvalLds e, int k0, int w, int la
     double lo = 0.0;
     if (act && !(NEMO_I8_ABLATE & 8)) {  // (8: instrumented build, no digits)
       const int i = ii[kk], j = jj[kk];
-      lo = log_fast(fma(sw[kk], elo_s[j] - 1.0, 1.0), ltab);
-      const double d = log_fast(fma(sw[kk], ehi_s[j] - 1.0, 1.0), ltab) - lo;
+      const double s1 = 1.0 - sw[kk];  // (1 - s first: delta_row, nemo_factored.hip)
+      lo = log_fast(fma(sw[kk], elo_s[j], s1), ltab);
+      const double d = log_fast(fma(sw[kk], ehi_s[j], s1), ltab) - lo;
       if constexpr (L2) i8l_digits<SPAD, ROWC>(A8, i, j, d);
       else i8o_digits<SPAD, ROWC>(A8, i, j, d, cexp);
     }
@@ -1856,8 +1858,9 @@ __device__ __forceinline__ void i8w_prep_passes(EvalLds e, int k0, int w, int la
       if (act) {
         const int i = e.perm[qr], j = e.perm[pp];
         const double sw = w01b[i * S + j];
-        const double lo = log_fast(fma(sw, elo_s[j] - 1.0, 1.0), ltab);
-        const double d = log_fast(fma(sw, ehi_s[j] - 1.0, 1.0), ltab) - lo;
+        const double s1 = 1.0 - sw;  // (1 - s first: delta_row, nemo_factored.hip)
+        const double lo = log_fast(fma(sw, elo_s[j], s1), ltab);
+        const double d = log_fast(fma(sw, ehi_s[j], s1), ltab) - lo;
         i8w_digits(A8, i, j, d);
         if (side_a) ga[kk] += lo;
         else gb[kk] += lo;
@@ -2348,13 +2351,15 @@ hipError_t stage_i8o(Ctx& c, const std::vector<double>& elo, const std::vector<d
       if ((err = copy_sync(c, c.d_udig, dig.data(), dig.size(), hipMemcpyHostToDevice)) != hipSuccess) return err;
       if ((err = copy_sync(c, c.d_u0, u0.data(), S * 8, hipMemcpyHostToDevice)) != hipSuccess) return err;
       c.i8o_diag = true;
-      // log2 fixed point: every entry v = delta 2^20 / ln 2 needs |rint(v)| <
-      // 2^25 - 2^17 - 2^6 (top digit in [-128, 127] after the balancing bias),
+      // log2 fixed point: every entry v = delta 2^20 / ln 2 needs rint(v) +
+      // 32 (1 + 64 + 4096) < 2^25 (top digit in [-128, 127] after the
+      // balancing bias 2^17 + 2^11 + 2^5; the 2^6 covers the rounding and
+      // the device's own Delta, a few ulps from this one),
       // and T_0 = (x / ln 2 + 1023) 2^20 must stay in (0, 2^31): |x| <= 690
       // (checked above) gives 27 < x / ln 2 + 1023 < 2019, and G + u0 rides
       // in T_0's C-init, so |G + u0| / ln 2 + 1023 < 2047
       constexpr double kLn2 = 0.69314718055994530942;
-      const double vmax = ldexp(1.0, 25) - ldexp(1.0, 17) - 128.0;
+      const double vmax = ldexp(1.0, 25) - ldexp(1.0, 17) - ldexp(1.0, 11) - 64.0;
       double dmax = 0.0, umax0 = 0.0;
       for (int j = 0; j < S; ++j) dmax = std::max(dmax, fabs(log(ehi[j]) - log(elo[j])));
       for (int i = 0; i < S; ++i) {

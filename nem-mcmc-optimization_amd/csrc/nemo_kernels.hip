@@ -67,12 +67,14 @@ __device__ __forceinline__ int xcd_work_index(int L, int N, int remap) {
 template <typename TT> struct Acc;
 template <> struct Acc<double> {
   using T = double;
-  __device__ static T term(double s, double v) { return fma(s, v - 1.0, 1.0); }
+  // 1 - s + s v with 1 - s formed first (exact for s >= 0.5): fma(s, v - 1, 1) loses v below 2^-53
+  // to the rounding of v - 1, all of it at s = 1 (log factors off by 1e-4 at v = e^-27)
+  __device__ static T term(double s, double v) { return fma(s, v, 1.0 - s); }
   __device__ static T renorm(T p, int& ex) { int e; T r = frexp(p, &e); ex += e; return r; }
 };
 template <> struct Acc<float> {
   using T = float;
-  __device__ static T term(float s, float v) { return fmaf(s, v - 1.0f, 1.0f); }
+  __device__ static T term(float s, float v) { return fmaf(s, v, 1.0f - s); }
   __device__ static T renorm(T p, int& ex) { int e; T r = frexpf(p, &e); ex += e; return r; }
 };
 

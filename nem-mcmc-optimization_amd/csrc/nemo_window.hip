@@ -83,8 +83,9 @@ __global__ __launch_bounds__(WAVES * kWave) void score_window_kernel(
     if (d <= cap && q >= d) {
       const int i = perm[q], j = perm[q - d];
       const double s = wb[(size_t)i * S + j];
-      flo = log(fma(s, e_lo[j] - 1.0, 1.0));
-      fhi = log(fma(s, e_hi[j] - 1.0, 1.0));
+      const double s1 = 1.0 - s;  // (1 - s first: delta_row, nemo_factored.hip)
+      flo = log(fma(s, e_lo[j], s1));
+      fhi = log(fma(s, e_hi[j], s1));
     }
     fac[k] = double2{flo, fhi};
   }
@@ -249,7 +250,8 @@ __global__ __launch_bounds__(WAVES * kWave, NEMO_WIN2_OCC) void score_window2_ke
     } else if (d <= cap && q >= d) {
       const int j = perm[q - d];
       const double sw = wb[(size_t)i * S + j];
-      f = double2{fma(sw, e_lo[j] - 1.0, 1.0), fma(sw, e_hi[j] - 1.0, 1.0)};
+      const double s1 = 1.0 - sw;  // (1 - s first: delta_row, nemo_factored.hip)
+      f = double2{fma(sw, e_lo[j], s1), fma(sw, e_hi[j], s1)};
     }
     ysc[8 * q + d] = f;
   }

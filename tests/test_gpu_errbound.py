@@ -85,11 +85,12 @@ def test_wide_model_auto_leaves_log2_kernel(wide):
     assert fk == 8 and bound == b_nat
     rng = np.random.default_rng(16000)
     perms = [rng.permutation(64) for _ in range(3)]
+    perms.append(perms[0])   # (after the three draws: the first three evaluations are as before)
     pos = np.array([_pos(p) for p in perms])
-    # weights across the range: random, saturated, all 0, all 1
+    # weights across the range: random, saturated, all 1, all 0
     w01 = np.stack([expit(rng.uniform(-3, 3, (64, 64))), expit(rng.uniform(-30, 30, (64, 64))),
-                    np.ones((64, 64))])
-    ref = np.array([no.order_score(m.U, t, perms[c], w01[c]) for c in range(3)])
+                    np.ones((64, 64)), np.zeros((64, 64))])
+    ref = np.array([no.order_score(m.U, t, perms[c], w01[c]) for c in range(4)])
     ll = eng.score(pos, w01)
     assert np.max(np.abs(ll - ref)) <= min(LL_TOL, bound + FP64_NOISE * 8)
     # forcing the log2 kernel: still within its own (larger) bound

@@ -122,7 +122,11 @@ def test_log2_digit_expansion_exact():
     the 7 slices are int8 (top digit of h in [-128, 127] up to |d| / ln 2 < 31.87,
     the others in [-32, 32]); the MFMA pairs rebuild h and l exactly."""
     rng = np.random.default_rng(3)
-    ds = np.concatenate([rng.uniform(-1, 1, 400) * 5.2, rng.uniform(-22.0, 22.0, 200), [0.0, 1e-12, -3.7]])
+    # ... up to stage_i8o's gate itself, |d| kL2Scale < 2^25 - 2^17 - 2^11 - 2^6 (the bias 2^17 + 2^11 +
+    # 2^5 on top of rint must stay below 2^25: test_fixed_point_ranges.py walks that edge)
+    edge = float(np.nextafter((2.0 ** 25 - 2.0 ** 17 - 2.0 ** 11 - 64.0) / L2_SCALE, 0.0))
+    ds = np.concatenate([rng.uniform(-1, 1, 400) * 5.2, rng.uniform(-22.0, 22.0, 200), [0.0, 1e-12, -3.7],
+                         [edge, -edge], rng.uniform(0.999, 1.0, 50) * edge, -rng.uniform(0.999, 1.0, 50) * edge])
     for d in ds:
         h, l, hd4, ld3 = l2_digits(float(d))
         assert -128 <= hd4[0] <= 127 and all(-32 <= q <= 31 for q in hd4[1:])
