@@ -282,7 +282,9 @@ struct LbOpts {
 // makes): x0 clipped, projected gradient, the generalised Cauchy point stops
 // at the bound when the model minimiser lies beyond it, unit first trial
 // step, stpmax from the bounds, forward differences flipped inside the box
-// (scipy _numdiff._adjust_scheme_to_bounds).  Written as a state machine
+// (scipy _numdiff._adjust_scheme_to_bounds), and the memory refreshed when the
+// variable re-enters the free set with pairs formk never updated (see the
+// direction loop).  Written as a state machine
 // with ONE evaluation site so the (large, fully unrolled) objective body is
 // instantiated once.  Python specification: oracle/lbfgsb1.py minimize_1d.
 template <bool BOUNDED, bool ANALYTIC, class FG>
@@ -297,6 +299,11 @@ __device__ __forceinline__ LbfgsResult lbfgsb1_minimize_opts(FG& fg, double x0, 
   int nfev = 0, nit = 0, ifun = 0;
   bool have_pair = false, in_ls = false;
   double s_last = 0.0, y_last = 0.0, theta = 1.0;
+  // BOUNDED: what formk's bookkeeping depends on (see the direction loop):
+  // the pairs in the memory (m = 10 at most), whether the last iteration
+  // stored one, whether its Cauchy point sat on a bound
+  int col = 0;
+  bool updatd = false, was_active = false;
   if (BOUNDED) x0 = dmin(dmax(x0, lo), hi);
   double x = x0, f = 0.0, g = 0.0;
   double z = 0.0, d = 0.0, stp = 0.0, xk = 0.0, fold = 0.0, gold = 0.0, gdold = 0.0;
@@ -364,6 +371,8 @@ __device__ __forceinline__ LbfgsResult lbfgsb1_minimize_opts(FG& fg, double x0, 
         if (uni(!have_pair)) return LbfgsResult{x, f, nit, nfev, 2};
         have_pair = false;
         theta = 1.0;
+        col = 0;
+        updatd = false;
       } else {
         ++nit;
         if (uni(fabs(lb::projg<BOUNDED>(x, g, has_lo, lo, has_hi, hi)) <= o.gtol)) return LbfgsResult{x, f, nit, nfev, 0};
@@ -376,11 +385,13 @@ __device__ __forceinline__ LbfgsResult lbfgsb1_minimize_opts(FG& fg, double x0, 
         double dr, ddum, s;
         if (stp == 1.0) { dr = gd - gdold; ddum = -gdold; s = d; }
         else { dr = (gd - gdold) * stp; s = d * stp; ddum = -gdold * stp; }
-        if (uni(!(dr <= kEpsMch * ddum))) {
+        updatd = !(dr <= kEpsMch * ddum);
+        if (uni(updatd)) {
           have_pair = true;
           s_last = s;
           y_last = r;
           theta = rr / dr;
+          col = col < 10 ? col + 1 : 10;
         }
       }
     }
@@ -389,10 +400,29 @@ __device__ __forceinline__ LbfgsResult lbfgsb1_minimize_opts(FG& fg, double x0, 
       double dtm;
       if (have_pair) { dtm = s_last / y_last; z = x + (-g) * dtm; }
       else { dtm = 1.0 / theta; z = x + dtm * (-g); }
+      bool active = false;  // the Cauchy point sits on a bound (nfree = 0)
       if (BOUNDED && g != 0.0) {
         // cauchy: the bound is the one breakpoint along -g
-        if (g > 0.0 && has_lo) { if (!(dtm < (x - lo) / g)) z = lo; }
-        else if (g < 0.0 && has_hi) { if (!(dtm < (hi - x) / (-g))) z = hi; }
+        if (g > 0.0 && has_lo) { if (!(dtm < (x - lo) / g)) { z = lo; active = true; } }
+        else if (g < 0.0 && has_hi) { if (!(dtm < (hi - x) / (-g))) { z = hi; active = true; } }
+      }
+      if (BOUNDED) {
+        // formk keeps N = [Y'ZZ'Y, ..; .., S'AA'S] up to date from the variables
+        // that enter and leave the free set, but it is skipped while no
+        // variable is free.  When the variable comes back, the rows of the pairs
+        // older than the newest never saw it leave: their S'AA'S entries go to
+        // -s_i s_j, K is not positive definite, and mainlb drops the memory and
+        // restarts the iteration with theta = 1 (lbfgsb.f "refresh the lbfgs
+        // memory"; no evaluation is spent).
+        if (uni(!active && was_active && col - (updatd ? 1 : 0) >= 1)) {
+          have_pair = false;
+          theta = 1.0;
+          col = 0;
+          updatd = false;
+          was_active = false;
+          continue;
+        }
+        was_active = active;
       }
       d = z - x;
       const double dnorm = sqrt(d * d);
@@ -424,6 +454,8 @@ __device__ __forceinline__ LbfgsResult lbfgsb1_minimize_opts(FG& fg, double x0, 
       if (uni(!have_pair)) return LbfgsResult{x, f, nit, nfev, 2};
       have_pair = false;
       theta = 1.0;
+      col = 0;
+      updatd = false;
     }
   }
 }

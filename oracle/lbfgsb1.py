@@ -199,7 +199,9 @@ def minimize_1d(fun, x0, ftol=0.01, gtol=0.01, eps=1e-8, maxls=20, maxiter=15000
     absolute step ``eps``.  With both bounds finite (the fixed-order methods,
     methods.py:95, :238, :384) L-BFGS-B 3.0 runs its constrained branch:
     x0 clipped, projected gradient, generalised Cauchy point with the bound
-    as breakpoint, unit first step and stpmax from the bounds."""
+    as breakpoint, unit first step and stpmax from the bounds; and formk's
+    refresh of the memory when the variable comes back from a bound with
+    pairs older than the newest in the memory (see the loop)."""
     nfev = 0
     cache = [None, 0.0, 0.0]   # scipy's ScalarFunction memoises the last (x, f, g)
     cnstnd = lo > -math.inf or hi < math.inf
@@ -245,6 +247,9 @@ def minimize_1d(fun, x0, ftol=0.01, gtol=0.01, eps=1e-8, maxls=20, maxiter=15000
     have_pair = False   # col > 0
     s_last = y_last = 0.0
     theta = 1.0
+    col = 0             # pairs in the memory (m = 10 at most)
+    updatd = False      # the last iteration stored a pair
+    was_active = False  # the last iteration's Cauchy point sat on a bound (nfree = 0)
     while True:
         # search direction d = z - x, z the subspace minimiser (lnsrlb works
         # with the rounded d, and evaluates the unit step at z itself):
@@ -258,6 +263,7 @@ def minimize_1d(fun, x0, ftol=0.01, gtol=0.01, eps=1e-8, maxls=20, maxiter=15000
         else:
             dtm = 1.0 / theta
             z = x + dtm * (-g)
+        active = False
         if cnstnd and g != 0.0:
             if g > 0.0 and lo > -math.inf:
                 dt, zb = (x - lo) / g, lo
@@ -267,6 +273,24 @@ def minimize_1d(fun, x0, ftol=0.01, gtol=0.01, eps=1e-8, maxls=20, maxiter=15000
                 dt = None
             if dt is not None and not (dtm < dt):
                 z = zb
+                active = True
+        if cnstnd:
+            # formk keeps N = [Y'ZZ'Y, ..; .., S'AA'S] up to date from the
+            # variables that enter and leave the free set, but it is skipped
+            # while no variable is free.  When the variable comes back, the rows
+            # of the pairs older than the newest never saw it leave: their
+            # S'AA'S entries go to -s_i s_j, K is not positive definite (for two
+            # pairs the pivot is -theta^2 s_1^2 / (theta + y_1/s_1 + y_2/s_2)),
+            # and mainlb refreshes the memory and restarts the iteration with
+            # theta = 1, without an evaluation
+            if not active and was_active and col - (1 if updatd else 0) >= 1:
+                have_pair = False
+                theta = 1.0
+                col = 0
+                updatd = False
+                was_active = False
+                continue
+            was_active = active
         d = z - x
         # lnsrlb
         dnorm = abs(d)  # scipy: dnrm2 (OpenBLAS, extended precision): |d| exactly for n = 1
@@ -314,6 +338,8 @@ def minimize_1d(fun, x0, ftol=0.01, gtol=0.01, eps=1e-8, maxls=20, maxiter=15000
                 return x, f, nit, nfev, ABNORMAL
             have_pair = False
             theta = 1.0
+            col = 0
+            updatd = False
             continue
         nit += 1
         if abs(projg(x, g)) <= gtol:
@@ -333,8 +359,10 @@ def minimize_1d(fun, x0, ftol=0.01, gtol=0.01, eps=1e-8, maxls=20, maxiter=15000
             dr = (gd - gdold) * stp
             s = d * stp
             ddum = -gdold * stp
-        if dr <= EPSMCH * ddum:
+        updatd = not (dr <= EPSMCH * ddum)
+        if not updatd:
             continue
+        col = min(col + 1, 10)
         have_pair = True
         s_last, y_last = s, r
         theta = rr / dr

@@ -13,6 +13,7 @@
 #include <random>
 #include <map>
 #include <set>
+#include <tuple>
 
 using namespace nemo::host;
 
@@ -133,9 +134,8 @@ static uint64_t mix(uint64_t h, uint64_t v) {
   return h * 0xff51afd7ed558ccdull;
 }
 
-static void check_inverse_schedule(std::mt19937_64& rng) {
-  for (int trial = 0; trial < 60; ++trial) {
-    const int S = 2 + (int)(rng() % 24), nprob = 1 + (int)(rng() % 3);
+static void check_inverse_schedule_case(std::mt19937_64& rng, int S, int nprob) {
+  {
     std::vector<int32_t> pos((size_t)nprob * S);
     for (int b = 0; b < nprob; ++b) {
       std::vector<int32_t> perm(S);
@@ -186,24 +186,22 @@ static void check_inverse_schedule(std::mt19937_64& rng) {
         const int i = (ent >> 8) & 0xff, k = ent & 0xff;
         return std::make_pair(perm[i], perm[k]);
       };
-      // reads(p) = entries (r, c) with b_p ~> c and r ~> a_p
-      auto reads = [&](int32_t p, int32_t q) {
-        const auto [ap, bp] = ab(p);
-        const auto [aq, bq] = ab(q);
-        return reach[(size_t)bq * S + bp] && reach[(size_t)ap * S + aq];
-      };
+      // reads(p) = entries (r, c) with b_p ~> c and r ~> a_p: pair p reads
+      // pair q when reach[b_q][b_p] && reach[a_p][a_q]
       std::vector<uint64_t> seq((size_t)S * S), par;
       for (size_t k = 0; k < seq.size(); ++k) seq[k] = k * 0x1234567ull + 1;
       par = seq;
       std::vector<std::vector<size_t>> rd(loop.size());  // entries each pair reads
       std::map<int32_t, size_t> at;
+      // ab() of the loop's pairs, once (the S > 64 cases have ~10^8 (p, q))
+      std::vector<int> la(loop.size()), lb(loop.size());
+      for (size_t p = 0; p < loop.size(); ++p) std::tie(la[p], lb[p]) = ab(loop[p]);
       for (size_t p = 0; p < loop.size(); ++p) {
         at[loop[p]] = p;
-        for (int32_t q : loop)
-          if (reads(loop[p], q)) {
-            const auto [aq, bq] = ab(q);
-            rd[p].push_back((size_t)aq * S + bq);
-          }
+        const char* from_b = &reach[0] + lb[p];            // reach[c][b_p]
+        const char* to_a = &reach[(size_t)la[p] * S];      // reach[a_p][r]
+        for (size_t q = 0; q < loop.size(); ++q)
+          if (from_b[(size_t)lb[q] * S] && to_a[la[q]]) rd[p].push_back((size_t)la[q] * S + lb[q]);
       }
       auto update = [&](const std::vector<uint64_t>& st, int32_t p) {
         uint64_t h = (uint64_t)p;
@@ -229,6 +227,18 @@ static void check_inverse_schedule(std::mt19937_64& rng) {
     }
     CHECK(seen.size() == sch.list.size() + sch.skip.size());
   }
+}
+
+static void check_inverse_schedule(std::mt19937_64& rng) {
+  for (int trial = 0; trial < 60; ++trial) {
+    const int S = 2 + (int)(rng() % 24), nprob = 1 + (int)(rng() % 3);
+    check_inverse_schedule_case(rng, S, nprob);
+  }
+  // reachability rows of W = (S + 63) / 64 words: W = 1 at its upper edge,
+  // W = 2 at its lower edge, W = 3 and W = 4 (the orders of 64 < S <= 256
+  // that column_solve<2> / <4> serve); two problems merge their levels
+  const int wide[][2] = {{64, 2}, {65, 1}, {65, 2}, {130, 2}, {200, 1}};
+  for (const auto& c : wide) check_inverse_schedule_case(rng, c[0], c[1]);
 }
 
 // ---- the asynchronous step queue ---------------------------------------------
