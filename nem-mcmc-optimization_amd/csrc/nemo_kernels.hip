@@ -74,7 +74,12 @@ template <> struct Acc<double> {
 };
 template <> struct Acc<float> {
   using T = float;
-  __device__ static T term(float s, float v) { return fmaf(s, v, 1.0f - s); }
+  // the factor formed in fp64 from the fp64 weight and rounded once.  With s and 1 - s as floats,
+  // 1.0f - (float)s is 0 for every s within 2^-25 of 1 (log factor -20 in place of -19.6 at
+  // s = 1 - 1e-9, T = -20), and a 1 - s rounded to fp32 on its own is off by up to 2^-25 in every
+  // factor of a (child, parent) pair, the same in all E columns: such an error does not average
+  // out over the columns, and moved the fixed-order optimizers' optima by 1e-6
+  __device__ static T term(double s, float v) { return (float)fma(s, (double)v, 1.0 - s); }
   __device__ static T renorm(T p, int& ex) { int e; T r = frexpf(p, &e); ex += e; return r; }
 };
 
@@ -164,13 +169,13 @@ __global__ __launch_bounds__(kScoreWaves * kWave) void score_kernel(
       for (int k = 0; k < 8; ++k) vv[k] = base[(size_t)jj[k] * E];
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
-        prod *= A::term((PT)ss[k], vv[k]);
+        prod *= A::term(ss[k], vv[k]);
         if (RENORM == 2 || (RENORM && (k & 3) == 3)) prod = A::renorm(prod, expo);
       }
     }
     for (; t < n; ++t) {
       const int j = rp[t];
-      prod *= A::term((PT)wp[t], base[(size_t)j * E]);
+      prod *= A::term(wp[t], base[(size_t)j * E]);
       if (RENORM) prod = A::renorm(prod, expo);
     }
     double cell = (double)U[(size_t)i * E + ec] + log((double)prod);
@@ -258,8 +263,12 @@ __global__ void prep_group_kernel(int S, int batch, int cap, const int32_t* __re
 }
 
 // grid = (ntiles, ngroups), block = GW waves; dynamic LDS: GW * (S-1) * CB
-// doubles of weights (wave-private), reused for the LSE merge.
-template <typename TT, int CB, int GW>
+// doubles of weights (wave-private), reused for the LSE merge.  The products
+// are fp64 for both table dtypes; a member without a parent of the union list
+// has weight 0 there, a factor of exactly 1.  RENORM: 0 the products as they
+// are; 1 renormalised after every 4th factor, and after every factor of the
+// tail (score_kernel's RENORM 1: needs_renorm).
+template <typename TT, int CB, int GW, int RENORM>
 __global__ __launch_bounds__(GW * kWave) void score_group_kernel(
     int S, int E, int ntiles, int batch, const TT* __restrict__ eT, const TT* __restrict__ U,
     const int32_t* __restrict__ rows, const double* __restrict__ sw,
@@ -286,9 +295,11 @@ __global__ __launch_bounds__(GW * kWave) void score_group_kernel(
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     const TT* base = eT + (size_t)i * S * E + ec;
+    using A = Acc<double>;
     double prod[CB];
+    int expo[CB];
 #pragma unroll
-    for (int q = 0; q < CB; ++q) prod[q] = 1.0;
+    for (int q = 0; q < CB; ++q) { prod[q] = 1.0; expo[q] = 0; }
     int t = 0;
     for (; t + 4 <= n; t += 4) {
       double vv[4];
@@ -296,19 +307,29 @@ __global__ __launch_bounds__(GW * kWave) void score_group_kernel(
       for (int k = 0; k < 4; ++k) vv[k] = (double)base[(size_t)rp[t + k] * E];
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
-        const double wv = vv[k] - 1.0;
 #pragma unroll
-        for (int q = 0; q < CB; ++q) prod[q] *= fma(wl[(t + k) * CB + q], wv, 1.0);
+        for (int q = 0; q < CB; ++q) prod[q] *= A::term(wl[(t + k) * CB + q], vv[k]);
+      }
+      if (RENORM) {
+#pragma unroll
+        for (int q = 0; q < CB; ++q) prod[q] = A::renorm(prod[q], expo[q]);
       }
     }
     for (; t < n; ++t) {
-      const double wv = (double)base[(size_t)rp[t] * E] - 1.0;
+      const double v = (double)base[(size_t)rp[t] * E];
 #pragma unroll
-      for (int q = 0; q < CB; ++q) prod[q] *= fma(wl[t * CB + q], wv, 1.0);
+      for (int q = 0; q < CB; ++q) {
+        prod[q] *= A::term(wl[t * CB + q], v);
+        if (RENORM) prod[q] = A::renorm(prod[q], expo[q]);
+      }
     }
     const double u = (double)U[(size_t)i * E + ec];
 #pragma unroll
-    for (int q = 0; q < CB; ++q) lse_push(m[q], l[q], u + log(prod[q]));
+    for (int q = 0; q < CB; ++q) {
+      double cell = u + log(prod[q]);
+      if (RENORM) cell += (double)expo[q] * kLn2;
+      lse_push(m[q], l[q], cell);
+    }
     __builtin_amdgcn_wave_barrier();
   }
   __syncthreads();
@@ -882,14 +903,16 @@ static hipError_t launch_group_t(Ctx& c, int batch, hipStream_t st) {
   const size_t mbytes = (size_t)2 * GW * CB * kWave * sizeof(double);
   const size_t lds = wbytes > mbytes ? wbytes : mbytes;
   dim3 grid(nt * ng);
-  if (c.dtype == 0)
-    score_group_kernel<double, CB, GW><<<grid, GW * kWave, lds, st>>>(
-        c.S, c.E, nt, batch, (const double*)c.d_eT, (const double*)c.d_U, c.d_grows, c.d_gsw,
-        c.d_gcnt, c.d_partial, c.xcd_remap);
-  else
-    score_group_kernel<float, CB, GW><<<grid, GW * kWave, lds, st>>>(
-        c.S, c.E, nt, batch, (const float*)c.d_eT, (const float*)c.d_U, c.d_grows, c.d_gsw,
-        c.d_gcnt, c.d_partial, c.xcd_remap);
+#define NEMO_SG(TT, RN)                                                                       \
+  score_group_kernel<TT, CB, GW, RN><<<grid, GW * kWave, lds, st>>>(                          \
+      c.S, c.E, nt, batch, (const TT*)c.d_eT, (const TT*)c.d_U, c.d_grows, c.d_gsw, c.d_gcnt, \
+      c.d_partial, c.xcd_remap)
+  if (c.dtype == 0) {
+    if (needs_renorm(c)) NEMO_SG(double, 1); else NEMO_SG(double, 0);
+  } else {
+    if (needs_renorm(c)) NEMO_SG(float, 1); else NEMO_SG(float, 0);
+  }
+#undef NEMO_SG
   return hipGetLastError();
 }
 

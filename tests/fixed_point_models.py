@@ -363,11 +363,14 @@ def inputs(s, seed=0):
     return perms, pos, np.stack([w for _, w in evals])
 
 
-def reference(u, t, perm, w01, cap=0):
+def reference(u, t, perm, w01, cap=0, full=False, et=None):
     """The oracle's operation in np.longdouble: cell[i] = U[i] + sum over the
     permissible parents j of log(1 - w + w exp(T[i][j])) (nemo_oracle.cell_ratios;
     with a cap the last ``cap`` predecessors), then the column log-sum-exp with
-    a max shift and its sum.  -> (ll, cs, min over i, e of cell - U[S])."""
+    a max shift and its sum.  -> (ll, cs, min over i, e of cell - U[S]);
+    ``full``: (ll, cs, cells (S + 1, E), order weights exp(cell - cs)), the
+    last three in long double.  ``et``: exp(T) in long double, when the caller
+    keeps it across evaluations."""
     ld = np.longdouble
     s = t.shape[0]
     perm = np.asarray(perm)
@@ -378,9 +381,12 @@ def reference(u, t, perm, w01, cap=0):
         pa = perm[max(0, p - cap) if cap else 0:p]
         if pa.size:
             w = w01[i, pa].astype(ld)[:, None]
-            cell[i] += np.log(one - w + w * np.exp(t[i, pa].astype(ld))).sum(axis=0)
+            v = np.exp(t[i, pa].astype(ld)) if et is None else et[i, pa]
+            cell[i] += np.log(one - w + w * v).sum(axis=0)
     m = cell.max(axis=0)
     cs = m + np.log(np.exp(cell - m).sum(axis=0))
+    if full:
+        return float(cs.sum()), cs, cell, np.exp(cell - cs)
     return float(cs.sum()), cs.astype(np.float64), float((cell[:s] - cell[s]).min())
 
 
