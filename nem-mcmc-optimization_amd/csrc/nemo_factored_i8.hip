@@ -128,6 +128,47 @@ struct EvalLds {
   int* perm;
 };
 
+// ---------------------------------------------------------------------------
+// The LDS of the offset kernels (score_i8o / i8l / i8s / i8p / i8w_kernel),
+// described once: the kernels carve from it and the launchers size from it.
+//   exp table [kExpTabN] x 8 B at LDS address 0 (exp2_fx_load), log table
+//   [128] x 16 B: one contiguous copy of Ctx::d_i8o_tabs (i8_copy_tables)
+//   elo_s, ehi_s [SPAD] f64 each
+//   NBUF evaluation buffers: G [SPAD] f64, gi [2][SPAD] int, perm [SPAD] int,
+//   A [NSL][KH][SPAD] rows of 64 B, swizzled (a_byte)
+// gi, perm and A together are the prep image of the split variant
+// (i8img_bytes).  score_i8_kernel keeps its own layout (no gi, 96-B rows).
+// ---------------------------------------------------------------------------
+constexpr int kExpTabN = 2048;  // exp_acc's table
+constexpr int kTabBytes = kExpTabN * 8 + 128 * 16;
+
+template <int SPAD, int NSL, int KH = 1, int NBUF = 1>
+struct I8Lds {
+  static constexpr int kElo = kTabBytes, kEhi = kElo + SPAD * 8, kBuf0 = kEhi + SPAD * 8;
+  // within one evaluation buffer
+  static constexpr int kG = 0, kGi = SPAD * 8, kPerm = kGi + 2 * SPAD * 4, kA = kPerm + SPAD * 4;
+  static constexpr int kABytes = NSL * KH * SPAD * 64, kBuf = kA + kABytes, kImg = kBuf - kGi;
+  static constexpr int kBytes = kBuf0 + NBUF * kBuf;
+  static_assert((kBuf0 + kGi) % 16 == 0 && kA % 16 == 0 && kBuf % 16 == 0, "16-B alignment of gi and A");
+  static_assert(NSL != 7 || KH != 1 || kImg == SPAD * kI8ImgRowBytes, "i8img_bytes follows this layout");
+
+  // launch size; a_min: least bytes of the A region (score_i8s_kernel reuses it)
+  static constexpr size_t bytes(size_t a_min = 0) {
+    return (size_t)kBytes + (a_min > (size_t)kABytes ? a_min - kABytes : 0);
+  }
+  static __device__ __forceinline__ double2* ltab(double* lds) { return (double2*)((char*)lds + kExpTabN * 8); }
+  static __device__ __forceinline__ double* elo(double* lds) { return (double*)((char*)lds + kElo); }
+  static __device__ __forceinline__ double* ehi(double* lds) { return (double*)((char*)lds + kEhi); }
+  static __device__ __forceinline__ EvalLds eval(double* lds, int k = 0) {
+    char* p = (char*)lds + kBuf0 + k * kBuf;
+    return EvalLds{(i32x4*)(p + kA), (double*)(p + kG), (int*)(p + kPerm)};
+  }
+  // [2][SPAD] G in fixed point, the C-inits g0, g1
+  static __device__ __forceinline__ int* gi(double* lds, int k = 0) {
+    return (int*)((char*)lds + kBuf0 + k * kBuf + kGi);
+  }
+};
+
 // perm from pos, G preset (0 / kPadG8 on padding rows), digits zeroed
 template <int SPAD, int NSL, int ROWC = kARow>
 __device__ __forceinline__ void i8_init_eval(EvalLds e, const int32_t* __restrict__ pb, int S, int tid,
@@ -141,11 +182,28 @@ __device__ __forceinline__ void i8_init_eval(EvalLds e, const int32_t* __restric
   for (int k = tid; k < NSL * SPAD * ROWC; k += nthreads) e.A[k] = i32x4{0, 0, 0, 0};
 }
 
-// Delta digits and G of one evaluation, passes [k0, k0 + KB) of this wave
-// (pass index k: q = w + k * WAVES).  Work runs in ORDER positions: the child
-// at position q has the parents at positions < q (within `cap`), so a pass
-// packs the children at positions q and S-1-q into one wave -- lane p < q:
-// (q, p); lane p >= q: (S-1-q, p-q) -- every lane one (child, parent) pair:
+// The prep passes (i8_prep_passes, i8o_prep_passes, i8w_prep_passes).  Work
+// runs in ORDER positions: the child at position q has the parents at
+// positions < q (within `cap`).  Uncapped ("packed"), pass q packs the
+// children at positions q and S-1-q into one wave -- slot p < q: (q, p), side
+// a; slot p >= q: (S-1-q, p-q), side b -- (S + 1) / 2 passes; capped, pass q
+// is child q alone with its nearest `cap` parents, S passes.  Each routine
+// decodes its slots and writes G back in place: either as a function call
+// changes the instruction mix of every kernel (MEASUREMENTS.md).
+__device__ __forceinline__ int i8_npass(int S, int cap) {
+  return (cap == 0 || cap >= S - 1) ? (S + 1) / 2 : S;
+}
+
+// wave w of WAVES takes the passes w, w + WAVES, ...: how many (pass index k:
+// q = w + k * WAVES; the prep routines do KB of them per call)
+template <int WAVES>
+__device__ __forceinline__ int i8_wave_passes(int S, int cap, int w) {
+  const int npass = i8_npass(S, cap);
+  return npass > w ? (npass - w + WAVES - 1) / WAVES : 0;
+}
+
+// Delta digits and G of one evaluation, passes [k0, k0 + KB) of this wave,
+// every lane one (child, parent) pair:
 //     lo = log(1 - w + w e^lo_j), Delta = log(1 - w + w e^hi_j) - lo
 // (nem_order_mcmc.py:83-86 per factor).  The weights of the KB passes are
 // fetched first and their G sums reduced together (independent butterflies).
@@ -401,10 +459,6 @@ __device__ __forceinline__ void i8o_prep_passes(EvalLds e, int k0, int w, int la
   }
 }
 
-__device__ __forceinline__ int i8_npass(int S, int cap) {
-  return (cap == 0 || cap >= S - 1) ? (S + 1) / 2 : S;
-}
-
 // One 16-effect tile, part 1: NP pairs of i8 MFMAs per row block and the
 // exact integer recombination into f64 cells (U + G + T_0 2^(c-24) +
 // T_1 2^(c-48)).  After this the U registers are free for the next tile.
@@ -439,6 +493,29 @@ __device__ __forceinline__ void i8_cells(const i32x4* __restrict__ Al, const dou
       cell[r][g] = v + uc[r][g];
     }
   }
+}
+
+// --- pieces every int8 score kernel shares --------------------------------
+constexpr double kLn2 = 0.69314718055994530942;
+
+// the sets [s_begin, s_end) of evaluation b that block `work` walks: `split`
+// consecutive blocks share an evaluation
+struct I8Block { int b, s_begin, s_end; };
+__device__ __forceinline__ I8Block i8_block(int nsets, int split, int remap) {
+  const int work = xcd_index8((int)blockIdx.x, (int)gridDim.x, remap);
+  const int b = work / split;
+  const int part = work - b * split;
+  const int spb = (nsets + split - 1) / split;
+  const int s_begin = part * spb;
+  return I8Block{b, s_begin, min(nsets, s_begin + spb)};
+}
+
+// a column's product over the tiles of a set, kept as mantissa * 2^lexp:
+// branch-free, no overflow
+__device__ __forceinline__ void i8_colprod(double& lprod, int& lexp, double l, bool valid) {
+  lprod *= valid ? l : 1.0;
+  lexp += __builtin_amdgcn_frexp_exp(lprod);
+  lprod = __builtin_amdgcn_frexp_mant(lprod);
 }
 
 // part 2: the column log-sum-exp over the SPAD rows and the null row, folded
@@ -477,15 +554,12 @@ __device__ __forceinline__ void i8_lse(double (&cell)[NR][4], double unull, bool
   l += __shfl_xor(l, 16, kWave);
   l += __shfl_xor(l, 32, kWave);
   l += exp_lse8(unull - m, etab);
-  // prod(l) kept as mantissa * 2^lexp: branch-free, no overflow
   msum += valid ? m : 0.0;
-  lprod *= valid ? l : 1.0;
-  lexp += __builtin_amdgcn_frexp_exp(lprod);
-  lprod = __builtin_amdgcn_frexp_mant(lprod);
+  i8_colprod(lprod, lexp, l, valid);
 }
 
 __device__ __forceinline__ double i8_set_value(double msum, double lprod, int lexp, int lane) {
-  double v = msum + (log(lprod) + (double)lexp * 0.69314718055994530942);
+  double v = msum + (log(lprod) + (double)lexp * kLn2);
   v = lane < 16 ? v : 0.0;
   return wsum(v);
 }
@@ -531,12 +605,8 @@ __global__ __launch_bounds__(WAVES * kWave, NEMO_I8_WAVES_PER_SIMD) void score_i
   ev.perm = (int*)(ev.G + SPAD);                         // [SPAD]
   ev.A = (i32x4*)(ev.perm + SPAD);                       // [NSL][SPAD][kARow]
 
-  const int work = xcd_index8((int)blockIdx.x, (int)gridDim.x, remap);
-  const int b = work / split;
-  const int part = work - b * split;
-  const int spb = (nsets + split - 1) / split;
-  const int s_begin = part * spb;
-  const int s_end = min(nsets, s_begin + spb);
+  const I8Block blk = i8_block(nsets, split, remap);
+  const int b = blk.b, s_begin = blk.s_begin, s_end = blk.s_end;
   const int tid = threadIdx.x;
   const int lane = tid & (kWave - 1);
   const int w = __builtin_amdgcn_readfirstlane(tid / kWave);
@@ -545,14 +615,9 @@ __global__ __launch_bounds__(WAVES * kWave, NEMO_I8_WAVES_PER_SIMD) void score_i
   i8_tables(etab, ltab, elo_s, ehi_s, e_lo, e_hi, S, SPAD, tid, blockDim.x);
   i8_init_eval<SPAD, NSL>(ev, pos + (size_t)b * S, S, tid, blockDim.x);
   __syncthreads();
-  {
-    constexpr int KB = 4;
-    const int npass = i8_npass(S, cap);
-    const int my = npass > w ? (npass - w + WAVES - 1) / WAVES : 0;
-    for (int k0 = 0; k0 < my; k0 += KB)
-      i8_prep_passes<SPAD, NSL, WAVES, KB>(ev, k0, w, lane, S, cap, cexp, w01 + (size_t)b * S * S,
-                                           elo_s, ehi_s, ltab);
-  }
+  for (int k0 = 0, my = i8_wave_passes<WAVES>(S, cap, w); k0 < my; k0 += 4)
+    i8_prep_passes<SPAD, NSL, WAVES, 4>(ev, k0, w, lane, S, cap, cexp, w01 + (size_t)b * S * S, elo_s,
+                                        ehi_s, ltab);
   // U rows of this lane's cells: 16r + 4rg + g (i8 C layout).  The staged U
   // has >= SPAD rows (rows S+1.. are zero; their G is kPadG8), so a cell's
   // address is a uniform part ((16r + g) E) + one per-lane offset (4 rg E + col).
@@ -608,15 +673,20 @@ __global__ __launch_bounds__(WAVES * kWave, NEMO_I8_WAVES_PER_SIMD) void score_i
       set = setn;
     }
   }
-  // one block per evaluation: it sums its own partials (same order as
-  // finalize_factored_kernel, so the bits match the split > 1 path)
   if (split == 1) {
-    __syncthreads();  // the block's partial stores are visible to the block
+    __syncthreads();
     if (w == 0) {
       const double v = sum_partials(partial + (size_t)b * nsets, nsets, lane);
       if (lane == 0) ll_out[b] = v;
     }
   }
+}
+
+// blocks per evaluation: fill `slots` block slots of the device; each split
+// re-derives its evaluation's digits (cheap next to its tiles)
+inline int i8_split(int slots, int batch, int nsets) {
+  const int split = (slots + batch - 1) / batch;
+  return split < 1 ? 1 : (split > nsets ? nsets : split);
 }
 
 template <int NR, int WAVES, int NP>
@@ -625,11 +695,7 @@ hipError_t launch_i8_t(Ctx& c, int batch, int cap, const int32_t* d_pos, const d
   constexpr int SPAD = NR * 16;
   const int ntiles = (c.E + 15) / 16;
   const int nsets = (ntiles + 7) / 8;
-  // blocks per evaluation: fill 2 waves per SIMD on 256 CUs; each split
-  // re-derives its evaluation's digits (cheap next to its tiles)
-  const int slots = 256 * (8 / WAVES);
-  int split = (slots + batch - 1) / batch;
-  split = split < 1 ? 1 : (split > nsets ? nsets : split);
+  const int split = i8_split(256 * (8 / WAVES), batch, nsets);  // 2 waves per SIMD on 256 CUs
   const size_t lds = 256 * 8 + 128 * 16 + 4 * SPAD * 8 + SPAD * 4 + (size_t)2 * NP * SPAD * 16 * kARow;
   const double sA = ldexp(1.0, c.i8_cexp - 24), sB = ldexp(1.0, c.i8_cexp - 48),
                sC = ldexp(1.0, c.i8_cexp - 60);
@@ -674,7 +740,6 @@ hipError_t launch_i8_t(Ctx& c, int batch, int cap, const int32_t* d_pos, const d
 // dword is stored as hi(2^(j/2048)) with its exponent field cleared, XOR
 // (j << 9), so one shift-xor makes the exponent field 1023 + (k >> 11) (no
 // ldexp; |x| <= 700 keeps it normal).  Table: kExpTabN entries, 16 KB.
-constexpr int kExpTabN = 2048;
 constexpr double kExpMagicB = 6755399441055744.0 + 1023.0 * 2048.0;
 
 __device__ __forceinline__ double exp_acc(double x, const uint2* __restrict__ tab, double acc) {
@@ -760,6 +825,73 @@ __device__ __forceinline__ double exp2_fx_apply(uint32_t t0, uint64_t ev, double
   return fma(__builtin_bit_cast(double, ((uint64_t)hi << 32) | (uint32_t)ev), p, acc);
 }
 
+// --- pieces the offset kernels share (layout: I8Lds); the log2 ones (i8l_*)
+// serve score_i8l / i8s / i8w_kernel and the two-tile walk ------------------
+// both tables (precomputed per context) in one contiguous 18 KB copy, and
+// e^lo / e^hi.  (The helpers step by an unsigned stride, as the loops they
+// replace stepped by blockDim.x: a signed one makes the compiler unroll them.)
+template <int SPAD>
+__device__ __forceinline__ void i8_copy_tables(double* lds, double* elo_s, double* ehi_s, const void* tabs,
+                                               const double* e_lo, const double* e_hi, int S, int tid,
+                                               unsigned nthreads) {
+  const int4* src = (const int4*)tabs;
+  int4* dst = (int4*)lds;
+  for (int k = tid; k < kTabBytes / 16; k += nthreads) dst[k] = src[k];
+  for (int i = tid; i < SPAD; i += nthreads) {
+    elo_s[i] = i < S ? e_lo[i] : 1.0;
+    ehi_s[i] = i < S ? e_hi[i] : 1.0;
+  }
+}
+
+// U' / ln 2 as the free diagonal "parent" i of child i (stage_i8o's log2
+// digits, 8 per row), slice 4 doubled (i8l_digits); KH K-halves of 64 parents
+template <int SPAD, int KH = 1>
+__device__ __forceinline__ void i8l_diag(i32x4* A, const int8_t* udig, int S, int tid, unsigned nthreads) {
+  constexpr int NSL = 7;
+  int8_t* A8 = (int8_t*)A;
+  for (int k = tid; k < S * NSL; k += nthreads) {
+    const int i = k / NSL, sl = k - i * NSL;
+    const int8_t d = udig[i * 8 + sl];
+    const int h = KH > 1 ? i >> 6 : 0, j = KH > 1 ? i & 63 : i;
+    A8[(sl * KH + h) * SPAD * 64 + a_byte<4>(i, j)] = sl == 4 ? (int8_t)(2 * d) : d;
+  }
+}
+
+// G + u0 in units of 2^-20 / ln 2: g0 = rint(.) + kL2Bias (the exponent bias
+// of exp2_fx_apply), g1 = the remainder in units of 2^-38 / ln 2 (the C-init
+// of slices 5-6); |g1| <= 2^17.  G is one value per row, so its rounding is
+// systematic over the effects: it gets T_1's full resolution.
+constexpr int kL2Bias = 1023 << 20;
+template <int SPAD>
+__device__ __forceinline__ void i8l_split_g(EvalLds e, int* gi, const double* __restrict__ u0, int S,
+                                            int tid, unsigned nthreads) {
+  for (int i = tid; i < SPAD; i += nthreads) {
+    const double g = i < S ? e.G[i] + u0[i] : e.G[i];
+    const double g0 = rint(g * kL2Scale);
+    gi[i] = (int)g0 + kL2Bias;
+    gi[SPAD + i] = (int)rint(fma(g, kL2Scale, -g0) * 262144.0);
+  }
+}
+
+// A set's partial from v, the per-lane log of its column products: every
+// 16-lane row holds 16 columns (rowsum4), a DPP sum within the row; PAIR
+// (the two-tile walks): row 0 holds the a tiles' columns and row 1 the b
+// tiles', so row 0's sum + row 1's
+template <bool PAIR>
+__device__ __forceinline__ void i8l_set_store(double v, int lane, const double* nullsum,
+                                              double* partial, size_t b, int nsets, int set) {
+  v = rowsum16(v);
+  if constexpr (PAIR) v += __shfl_down(v, 16, kWave);
+  if (lane == 0) partial[b * nsets + set] = nullsum[set] + v;
+}
+// ... from the products themselves: log_fast (lprod is a mantissa in [0.5, 1))
+template <bool PAIR>
+__device__ __forceinline__ void i8l_set_finish(double lprod, int lexp, const double2* ltab, int lane,
+                                               const double* nullsum, double* partial, size_t b, int nsets,
+                                               int set) {
+  i8l_set_store<PAIR>(log_fast(lprod, ltab) + (double)lexp * kLn2, lane, nullsum, partial, b, nsets, set);
+}
+
 template <int NR, int WAVES, bool DIAG>
 __global__ __launch_bounds__(WAVES * kWave, NEMO_I8O_WAVES_PER_SIMD) void score_i8o_kernel(
     int S, int E, int ntiles, int nsets, int split, int cap, int cexp, double padg,
@@ -772,54 +904,35 @@ __global__ __launch_bounds__(WAVES * kWave, NEMO_I8O_WAVES_PER_SIMD) void score_
   constexpr int SPAD = NR * 16;
   constexpr int NP = 4;
   constexpr int NSL = 2 * NP;
+  using L = I8Lds<SPAD, NSL>;
   extern __shared__ __attribute__((aligned(16))) double lds8[];
-  uint2* etab_o = (uint2*)lds8;                          // [kExpTabN] exp_acc's table
-  double2* ltab = (double2*)(etab_o + kExpTabN);         // [128] log table
-  double* elo_s = (double*)(ltab + 128);                 // [SPAD] e^lo_j
-  double* ehi_s = elo_s + SPAD;                          // [SPAD] e^hi_j
-  EvalLds ev;
-  ev.G = ehi_s + SPAD;                                   // [SPAD]
-  int* gi = (int*)(ev.G + SPAD);                         // [2][SPAD] g0, g1
-  ev.perm = gi + 2 * SPAD;                               // [SPAD]
-  ev.A = (i32x4*)(ev.perm + SPAD);                       // [NSL][SPAD][4] swizzled (a_byte)
+  const uint2* etab_o = (const uint2*)lds8;  // exp_acc's table
+  double2* ltab = L::ltab(lds8);
+  double *elo_s = L::elo(lds8), *ehi_s = L::ehi(lds8);
+  const EvalLds ev = L::eval(lds8);
+  int* gi = L::gi(lds8);
 
-  const int work = xcd_index8((int)blockIdx.x, (int)gridDim.x, remap);
-  const int b = work / split;
-  const int part = work - b * split;
-  const int spb = (nsets + split - 1) / split;
-  const int s_begin = part * spb;
-  const int s_end = min(nsets, s_begin + spb);
+  const I8Block blk = i8_block(nsets, split, remap);
+  const int b = blk.b, s_begin = blk.s_begin, s_end = blk.s_end;
   const int tid = threadIdx.x;
   const int lane = tid & (kWave - 1);
   const int w = __builtin_amdgcn_readfirstlane(tid / kWave);
   const int col = lane & 15, rg = lane >> 4;
 
-  {  // both tables (precomputed per context) in one contiguous 18 KB copy
-    const int4* src = (const int4*)tabs;
-    int4* dst = (int4*)lds8;
-    for (int k = tid; k < (kExpTabN * 8 + 128 * 16) / 16; k += blockDim.x) dst[k] = src[k];
-    for (int i = tid; i < SPAD; i += blockDim.x) {
-      elo_s[i] = i < S ? e_lo[i] : 1.0;
-      ehi_s[i] = i < S ? e_hi[i] : 1.0;
-    }
-  }
+  i8_copy_tables<SPAD>(lds8, elo_s, ehi_s, tabs, e_lo, e_hi, S, tid, blockDim.x);
   i8_init_eval<SPAD, NSL, 4>(ev, pos + (size_t)b * S, S, tid, blockDim.x, padg);
   __syncthreads();
-  if constexpr (DIAG) {  // U' as the free diagonal "parent" i of child i (stage_i8o)
+  // U' as the free diagonal "parent" i of child i (stage_i8o; 8 slices: not i8l_diag)
+  if constexpr (DIAG) {
     int8_t* A8 = (int8_t*)ev.A;
     for (int k = tid; k < S * NSL; k += blockDim.x) {
       const int i = k / NSL, sl = k - i * NSL;
       A8[sl * SPAD * 64 + a_byte<4>(i, i)] = udig[k];
     }
   }
-  {
-    constexpr int KB = 4;
-    const int npass = i8_npass(S, cap);
-    const int my = npass > w ? (npass - w + WAVES - 1) / WAVES : 0;
-    for (int k0 = 0; k0 < my; k0 += KB)
-      i8o_prep_passes<SPAD, WAVES, KB, 4>(ev, k0, w, lane, S, cap, cexp, w01 + (size_t)b * S * S,
-                                          elo_s, ehi_s, ltab);
-  }
+  for (int k0 = 0, my = i8_wave_passes<WAVES>(S, cap, w); k0 < my; k0 += 4)
+    i8o_prep_passes<SPAD, WAVES, 4, 4>(ev, k0, w, lane, S, cap, cexp, w01 + (size_t)b * S * S, elo_s,
+                                       ehi_s, ltab);
   __syncthreads();
   // G in fixed point: g0 = rint(G 2^(24-c)), g1 = rint((G - g0 2^(c-24)) 2^(48-c))
   for (int i = tid; i < SPAD; i += blockDim.x) {
@@ -906,12 +1019,9 @@ __global__ __launch_bounds__(WAVES * kWave, NEMO_I8O_WAVES_PER_SIMD) void score_
 #endif
         }
       }
-      double l = rowsum4(ls0 + ls1) + 1.0;  // + e^0 of the null row
-      lprod *= t * 16 + col < E ? l : 1.0;
-      lexp += __builtin_amdgcn_frexp_exp(lprod);
-      lprod = __builtin_amdgcn_frexp_mant(lprod);
-      if (setn != set) {  // set complete: one partial
-        double v = log(lprod) + (double)lexp * 0.69314718055994530942;
+      i8_colprod(lprod, lexp, rowsum4(ls0 + ls1) + 1.0, t * 16 + col < E);  // + e^0 of the null row
+      if (setn != set) {  // set complete: one partial (libm's log and a full-wave sum: not i8l_set_finish)
+        double v = log(lprod) + (double)lexp * kLn2;
         v = wsum(lane < 16 ? v : 0.0);
         if (lane == 0) partial[(size_t)b * nsets + set] = nullsum[set] + v;
         lprod = 1.0;
@@ -937,10 +1047,8 @@ hipError_t launch_i8o_t(Ctx& c, int batch, int cap, const int32_t* d_pos, const 
   constexpr int SPAD = NR * 16;
   const int ntiles = (c.E + 15) / 16;
   const int nsets = (ntiles + 7) / 8;
-  const int slots = 256 * (NEMO_I8O_WAVES_PER_SIMD * 4 / WAVES);
-  int split = (slots + batch - 1) / batch;
-  split = split < 1 ? 1 : (split > nsets ? nsets : split);
-  const size_t lds = kExpTabN * 8 + 128 * 16 + 3 * SPAD * 8 + 3 * SPAD * 4 + (size_t)8 * SPAD * 64;
+  const int split = i8_split(256 * (NEMO_I8O_WAVES_PER_SIMD * 4 / WAVES), batch, nsets);
+  const size_t lds = I8Lds<SPAD, 8>::bytes();
   const double sA = ldexp(1.0, c.i8_cexp - 24), sB = ldexp(1.0, c.i8_cexp - 48);
   score_i8o_kernel<NR, WAVES, DIAG><<<dim3(batch * split), WAVES * kWave, lds, st>>>(
       c.S, c.E, ntiles, nsets, split, cap, c.i8_cexp, c.i8o_padg, d_pos, d_w01, c.d_elo, c.d_ehi,
@@ -1099,6 +1207,7 @@ __device__ __forceinline__ int i8l_walk2(const i32x4* __restrict__ Al0, const i3
         }
         auto epi = [&](const i32x4 h0, const i32x4 h1, const i32x4 l0, const i32x4 l1, double& ls0,
                        double& ls1) {
+          // the log2 cell epilogue (see score_i8l_kernel's one-tile walk)
           uint32_t t0[4];
           uint64_t evv[4];
           double pr[4];
@@ -1126,17 +1235,9 @@ __device__ __forceinline__ int i8l_walk2(const i32x4* __restrict__ Al0, const i3
       const double l = rowsum_pair(la0 + la1, lb0 + lb1) + 1.0;  // + e^0 of the null row
       const bool tb = (lane & 16) != 0;
       const bool ok = (((tb ? t2 : t) * 16 + col) < E) & (two | !tb);  // branch-free (bitwise)
-      lprod *= ok ? l : 1.0;
-      lexp += __builtin_amdgcn_frexp_exp(lprod);
-      lprod = __builtin_amdgcn_frexp_mant(lprod);
+      i8_colprod(lprod, lexp, l, ok);
       if (setn != set) {  // set complete: one partial
-        // row 0 holds the 16 column products of the set's a tiles, row 1 those
-        // of its b tiles: log_fast (lprod is a mantissa in [0.5, 1)), a DPP sum
-        // within each row, then row 0's sum + row 1's
-        double v = log_fast(lprod, ltab) + (double)lexp * 0.69314718055994530942;
-        v = rowsum16(v);
-        v += __shfl_down(v, 16, kWave);
-        if (lane == 0) partial[(size_t)b * nsets + set] = nullsum[set] + v;
+        i8l_set_finish<true>(lprod, lexp, ltab, lane, nullsum, partial, b, nsets, set);
         lprod = 1.0;
         lexp = 0;
       }
@@ -1196,17 +1297,14 @@ __global__ __launch_bounds__(WAVES * kWave, OCC) void score_i8l_kernel(
     int4* __restrict__ img = nullptr) {
   constexpr int SPAD = NR * 16;
   constexpr int NSL = 7;
+  using L = I8Lds<SPAD, NSL>;
   extern __shared__ __attribute__((aligned(16))) double lds8[];
-  uint2* etab_o = (uint2*)lds8;                          // [kExpTabN] at LDS address 0
-  double2* ltab = (double2*)(etab_o + kExpTabN);         // [128] log table
-  double* elo_s = (double*)(ltab + 128);                 // [SPAD] e^lo_j
-  double* ehi_s = elo_s + SPAD;                          // [SPAD] e^hi_j
-  EvalLds ev;
-  ev.G = ehi_s + SPAD;                                   // [SPAD]
-  int* gi = (int*)(ev.G + SPAD);                         // [2][SPAD] g0, g1
-  ev.perm = gi + 2 * SPAD;                               // [SPAD]
-  ev.A = (i32x4*)(ev.perm + SPAD);                       // [NSL][SPAD][4] swizzled (a_byte)
+  double2* ltab = L::ltab(lds8);
+  double *elo_s = L::elo(lds8), *ehi_s = L::ehi(lds8);
+  const EvalLds ev = L::eval(lds8);
+  int* gi = L::gi(lds8);
 
+  // (i8_block, in place: the call changes the prep-only kernel's registers)
   const int work = xcd_index8((int)blockIdx.x, (int)gridDim.x, remap);
   const int b = work / split;
   const int part = work - b * split;
@@ -1218,13 +1316,11 @@ __global__ __launch_bounds__(WAVES * kWave, OCC) void score_i8l_kernel(
   const int w = __builtin_amdgcn_readfirstlane(tid / kWave);
   const int col = lane & 15, rg = lane >> 4;
 
-  constexpr int kImg4 = SPAD * 460 / 16;  // the image in int4: gi, perm, digits (i8img_bytes)
-  {  // both tables (precomputed per context) in one contiguous 18 KB copy
-    // (the prep-only launch needs the log table alone)
+  constexpr int kImg4 = L::kImg / 16;  // the prep image in int4: gi, perm, digits
+  {  // i8_copy_tables with MODE 1's start (log table alone) and MODE 2's skip
     const int4* src = (const int4*)tabs;
     int4* dst = (int4*)lds8;
-    for (int k = tid + (MODE == 1 ? kExpTabN * 8 / 16 : 0); k < (kExpTabN * 8 + 128 * 16) / 16;
-         k += blockDim.x)
+    for (int k = tid + (MODE == 1 ? kExpTabN * 8 / 16 : 0); k < kTabBytes / 16; k += blockDim.x)
       dst[k] = src[k];
     if constexpr (MODE != 2)
       for (int i = tid; i < SPAD; i += blockDim.x) {
@@ -1238,43 +1334,22 @@ __global__ __launch_bounds__(WAVES * kWave, OCC) void score_i8l_kernel(
     for (int k = tid; k < kImg4; k += blockDim.x) dst[k] = src[k];
     __syncthreads();
   } else {
-  i8_init_eval<SPAD, NSL, 4>(ev, pos + (size_t)b * S, S, tid, blockDim.x, padg);
-  __syncthreads();
-  {  // U' / ln 2 as the free diagonal "parent" i of child i
-    int8_t* A8 = (int8_t*)ev.A;
-    for (int k = tid; k < S * NSL; k += blockDim.x) {
-      const int i = k / NSL, sl = k - i * NSL;
-      const int8_t d = udig[i * 8 + sl];
-      A8[sl * SPAD * 64 + a_byte<4>(i, i)] = sl == 4 ? (int8_t)(2 * d) : d;  // slice 4 doubled (i8l_digits)
+    i8_init_eval<SPAD, NSL, 4>(ev, pos + (size_t)b * S, S, tid, blockDim.x, padg);
+    __syncthreads();
+    i8l_diag<SPAD>(ev.A, udig, S, tid, blockDim.x);
+    for (int k0 = 0, my = i8_wave_passes<WAVES>(S, cap, w); k0 < my; k0 += 4)
+      i8o_prep_passes<SPAD, WAVES, 4, 4, true>(ev, k0, w, lane, S, cap, 0, w01 + (size_t)b * S * S, elo_s,
+                                               ehi_s, ltab);
+    __syncthreads();
+    i8l_split_g<SPAD>(ev, gi, u0, S, tid, blockDim.x);
+    __syncthreads();
+    if constexpr (MODE == 1) {
+      const int4* src = (const int4*)gi;
+      int4* dst = img + (size_t)b * kImg4;
+      for (int k = tid; k < kImg4; k += blockDim.x) dst[k] = src[k];
+      return;
     }
   }
-  {
-    constexpr int KB = 4;
-    const int npass = i8_npass(S, cap);
-    const int my = npass > w ? (npass - w + WAVES - 1) / WAVES : 0;
-    for (int k0 = 0; k0 < my; k0 += KB)
-      i8o_prep_passes<SPAD, WAVES, KB, 4, true>(ev, k0, w, lane, S, cap, 0, w01 + (size_t)b * S * S,
-                                                elo_s, ehi_s, ltab);
-  }
-  __syncthreads();
-  // G + u0 in units of 2^-20 / ln 2: g0 = rint(.) + (1023 << 20) (the exponent
-  // bias of exp2_fx_acc), g1 = the remainder in units of 2^-38 / ln 2 (the
-  // C-init of slices 5-6); |g1| <= 2^17.  G is one value per row, so its
-  // rounding is systematic over the effects: it gets T_1's full resolution.
-  for (int i = tid; i < SPAD; i += blockDim.x) {
-    const double g = i < S ? ev.G[i] + u0[i] : ev.G[i];
-    const double g0 = rint(g * kL2Scale);
-    gi[i] = (int)g0 + (1023 << 20);
-    gi[SPAD + i] = (int)rint(fma(g, kL2Scale, -g0) * 262144.0);
-  }
-  __syncthreads();
-  if constexpr (MODE == 1) {
-    const int4* src = (const int4*)gi;
-    int4* dst = img + (size_t)b * kImg4;
-    for (int k = tid; k < kImg4; k += blockDim.x) dst[k] = src[k];
-    return;
-  }
-  }  // MODE != 2
 #if NEMO_I8_ABLATE & 32  // instrumented build (tools/ablate.sh): prep only, no tiles
   if (s_end > 0) return;
 #endif
@@ -1328,37 +1403,32 @@ __global__ __launch_bounds__(WAVES * kWave, OCC) void score_i8l_kernel(
           i32x4 l1 = __builtin_amdgcn_mfma_i32_16x16x64_i8(A(5), b64, c1, 0, 0, 0);
           l1 = __builtin_amdgcn_mfma_i32_16x16x64_i8(A(6), b1, l1, 0, 0, 0);
   #endif
-          // the row block's 4 cells per lane in three phases, so the 4 table
-          // reads (random entries: ~3.5-way bank conflicts) are in flight
-          // while the series runs: addresses + reads, series, then assembly
+          // The log2 cell epilogue: the row block's 4 cells per lane in three phases,
+          // so the 4 table reads (random entries: ~3.5-way bank conflicts) are in
+          // flight while the series runs: addresses + reads, series, then assembly.
+          // (In place in every walk: as a shared function it changes the walks'
+          // register allocation.)
           uint32_t t0[4];
-          uint64_t ev[4];
+          uint64_t evv[4];
           double pr[4];
-  #pragma unroll
+#pragma unroll
           for (int g = 0; g < 4; ++g) {
             // T_0 wraps mod 2^32 only transiently (its true value is in (0, 2^31))
             t0[g] = ((uint32_t)h0[g] << 12) + (uint32_t)h1[g];
-            ev[g] = exp2_fx_load(t0[g]);
+            evv[g] = exp2_fx_load(t0[g]);
           }
-  #pragma unroll
+#pragma unroll
           for (int g = 0; g < 4; ++g)
             pr[g] = exp2_fx_series(t0[g], (int)(((uint32_t)l0[g] << 11) + (uint32_t)l1[g]));
-  #pragma unroll
+#pragma unroll
           for (int g = 0; g < 4; ++g) {
-            if (g & 1) ls1 = exp2_fx_apply(t0[g], ev[g], pr[g], ls1);
-            else ls0 = exp2_fx_apply(t0[g], ev[g], pr[g], ls0);
+            if (g & 1) ls1 = exp2_fx_apply(t0[g], evv[g], pr[g], ls1);
+            else ls0 = exp2_fx_apply(t0[g], evv[g], pr[g], ls0);
           }
         }
-        double l = rowsum4(ls0 + ls1) + 1.0;  // + e^0 of the null row
-        lprod *= t * 16 + col < E ? l : 1.0;
-        lexp += __builtin_amdgcn_frexp_exp(lprod);
-        lprod = __builtin_amdgcn_frexp_mant(lprod);
+        i8_colprod(lprod, lexp, rowsum4(ls0 + ls1) + 1.0, t * 16 + col < E);  // + e^0 of the null row
         if (setn != set) {  // set complete: one partial
-          // every 16-lane row holds the 16 column products (rowsum4): log_fast
-          // (lprod is a mantissa in [0.5, 1)) and a DPP sum within the row
-          double v = log_fast(lprod, ltab) + (double)lexp * 0.69314718055994530942;
-          v = rowsum16(v);
-          if (lane == 0) partial[(size_t)b * nsets + set] = nullsum[set] + v;
+          i8l_set_finish<false>(lprod, lexp, ltab, lane, nullsum, partial, b, nsets, set);
           lprod = 1.0;
           lexp = 0;
         }
@@ -1373,8 +1443,8 @@ __global__ __launch_bounds__(WAVES * kWave, OCC) void score_i8l_kernel(
     // arithmetic per cell and the same order of the column products as TT = 1,
     // so the same bits.  The second tile of a set's odd tail repeats the first
     // and is not multiplied in.
-    i8l_walk2<NR, WAVES, NEMO_I8L_PINGPONG != 0>(ev.A, Gi, Bt, Bt64, set, s_end, ntiles, E, col, lane, a_lane, nullsum, partial, b,
-                         nsets, ltab, [](int) {});
+    i8l_walk2<NR, WAVES, NEMO_I8L_PINGPONG != 0>(ev.A, Gi, Bt, Bt64, set, s_end, ntiles, E, col, lane, a_lane,
+                                                 nullsum, partial, b, nsets, ltab, [](int) {});
   }
   if (split == 1) {
     __syncthreads();
@@ -1400,6 +1470,8 @@ __global__ __launch_bounds__(WAVES * kWave, OCC) void score_i8l_kernel(
 // log).  Partials are per set, as in score_i8l_kernel, so ll bits do not
 // depend on the batch size or the block split.
 // ---------------------------------------------------------------------------
+constexpr size_t kI8sColsum = 16384;  // bytes of the column-sum buffer (below), whatever NR
+
 template <int NR>
 __global__ __launch_bounds__(8 * kWave, NEMO_I8O_WAVES_PER_SIMD) void score_i8s_kernel(
     int S, int E, int ntiles, int nsets, int split, int cap, double padg,
@@ -1412,66 +1484,33 @@ __global__ __launch_bounds__(8 * kWave, NEMO_I8O_WAVES_PER_SIMD) void score_i8s_
   constexpr int SPAD = NR * 16;
   constexpr int NSL = 7;
   constexpr int NG = WAVES / NR;                          // groups of row-block waves
+  using L = I8Lds<SPAD, NSL>;
   extern __shared__ __attribute__((aligned(16))) double lds8[];
-  uint2* etab_o = (uint2*)lds8;                          // [kExpTabN] at LDS address 0
-  double2* ltab = (double2*)(etab_o + kExpTabN);         // [128] log table
-  double* elo_s = (double*)(ltab + 128);                 // [SPAD] e^lo_j
-  double* ehi_s = elo_s + SPAD;                          // [SPAD] e^hi_j
-  EvalLds ev;
-  ev.G = ehi_s + SPAD;                                   // [SPAD]
-  int* gi = (int*)(ev.G + SPAD);                         // [2][SPAD] g0, g1
-  ev.perm = gi + 2 * SPAD;                               // [SPAD]
-  ev.A = (i32x4*)(ev.perm + SPAD);                       // [NSL][SPAD][4] swizzled (a_byte)
+  double2* ltab = L::ltab(lds8);
+  double *elo_s = L::elo(lds8), *ehi_s = L::ehi(lds8);
+  const EvalLds ev = L::eval(lds8);
+  int* gi = L::gi(lds8);
   // after the A fragments are in registers the same region holds the
-  // row-block column sums: [NG][2 (parity)][8 tiles][NR][16] doubles (16 KB)
+  // row-block column sums: [NG][2 (parity)][8 tiles][NR][16] doubles (kI8sColsum)
   double* colsum = (double*)ev.A;
 
-  const int work = xcd_index8((int)blockIdx.x, (int)gridDim.x, remap);
-  const int b = work / split;
-  const int part = work - b * split;
-  const int spb = (nsets + split - 1) / split;
-  const int s_begin = part * spb;
-  const int s_end = min(nsets, s_begin + spb);
+  const I8Block blk = i8_block(nsets, split, remap);
+  const int b = blk.b, s_begin = blk.s_begin, s_end = blk.s_end;
   const int tid = threadIdx.x;
   const int lane = tid & (kWave - 1);
   const int w = __builtin_amdgcn_readfirstlane(tid / kWave);
   const int rb = w % NR, grp = w / NR;
   const int col = lane & 15, rg = lane >> 4;
 
-  {  // both tables (precomputed per context) in one contiguous 18 KB copy
-    const int4* src = (const int4*)tabs;
-    int4* dst = (int4*)lds8;
-    for (int k = tid; k < (kExpTabN * 8 + 128 * 16) / 16; k += blockDim.x) dst[k] = src[k];
-    for (int i = tid; i < SPAD; i += blockDim.x) {
-      elo_s[i] = i < S ? e_lo[i] : 1.0;
-      ehi_s[i] = i < S ? e_hi[i] : 1.0;
-    }
-  }
+  i8_copy_tables<SPAD>(lds8, elo_s, ehi_s, tabs, e_lo, e_hi, S, tid, blockDim.x);
   i8_init_eval<SPAD, NSL, 4>(ev, pos + (size_t)b * S, S, tid, blockDim.x, padg);
   __syncthreads();
-  {  // U' / ln 2 as the free diagonal "parent" i of child i
-    int8_t* A8 = (int8_t*)ev.A;
-    for (int k = tid; k < S * NSL; k += blockDim.x) {
-      const int i = k / NSL, sl = k - i * NSL;
-      const int8_t d = udig[i * 8 + sl];
-      A8[sl * SPAD * 64 + a_byte<4>(i, i)] = sl == 4 ? (int8_t)(2 * d) : d;  // slice 4 doubled (i8l_digits)
-    }
-  }
-  {
-    constexpr int KB = 4;
-    const int npass = i8_npass(S, cap);
-    const int my = npass > w ? (npass - w + WAVES - 1) / WAVES : 0;
-    for (int k0 = 0; k0 < my; k0 += KB)
-      i8o_prep_passes<SPAD, WAVES, KB, 4, true>(ev, k0, w, lane, S, cap, 0, w01 + (size_t)b * S * S,
-                                                elo_s, ehi_s, ltab);
-  }
+  i8l_diag<SPAD>(ev.A, udig, S, tid, blockDim.x);
+  for (int k0 = 0, my = i8_wave_passes<WAVES>(S, cap, w); k0 < my; k0 += 4)
+    i8o_prep_passes<SPAD, WAVES, 4, 4, true>(ev, k0, w, lane, S, cap, 0, w01 + (size_t)b * S * S, elo_s,
+                                             ehi_s, ltab);
   __syncthreads();
-  for (int i = tid; i < SPAD; i += blockDim.x) {  // G + u0 as in score_i8l_kernel
-    const double g = i < S ? ev.G[i] + u0[i] : ev.G[i];
-    const double g0 = rint(g * kL2Scale);
-    gi[i] = (int)g0 + (1023 << 20);
-    gi[SPAD + i] = (int)rint(fma(g, kL2Scale, -g0) * 262144.0);
-  }
+  i8l_split_g<SPAD>(ev, gi, u0, S, tid, blockDim.x);
   __syncthreads();
   // this wave's row block: A fragments and G C-inits into registers
   i32x4 af[NSL];
@@ -1510,18 +1549,20 @@ __global__ __launch_bounds__(8 * kWave, NEMO_I8O_WAVES_PER_SIMD) void score_i8s_
         const i32x4 l0 = __builtin_amdgcn_mfma_i32_16x16x64_i8(af[4], b1, i32x4{0, 0, 0, 0}, 0, 0, 0);
         const i32x4 l1 = __builtin_amdgcn_mfma_i32_16x16x64_i8(
             af[6], b1, __builtin_amdgcn_mfma_i32_16x16x64_i8(af[5], b64, c1, 0, 0, 0), 0, 0, 0);
+        double ls0 = 0.0, ls1 = 0.0;
+        // the log2 cell epilogue (see score_i8l_kernel's one-tile walk)
         uint32_t t0[4];
         uint64_t evt[4];
         double pr[4];
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
+          // T_0 wraps mod 2^32 only transiently (its true value is in (0, 2^31))
           t0[g] = ((uint32_t)h0[g] << 12) + (uint32_t)h1[g];
           evt[g] = exp2_fx_load(t0[g]);
         }
 #pragma unroll
         for (int g = 0; g < 4; ++g)
           pr[g] = exp2_fx_series(t0[g], (int)(((uint32_t)l0[g] << 11) + (uint32_t)l1[g]));
-        double ls0 = 0.0, ls1 = 0.0;
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
           if (g & 1) ls1 = exp2_fx_apply(t0[g], evt[g], pr[g], ls1);
@@ -1542,11 +1583,10 @@ __global__ __launch_bounds__(8 * kWave, NEMO_I8O_WAVES_PER_SIMD) void score_i8s_
         double l = 1.0;  // + e^0 of the null row
 #pragma unroll
         for (int q = 0; q < NR; ++q) l += cs[(tt * NR + q) * 16 + col];
-        lp *= t < ntiles && t * 16 + col < E ? l : 1.0;
-        le += __builtin_amdgcn_frexp_exp(lp);
-        lp = __builtin_amdgcn_frexp_mant(lp);
+        i8_colprod(lp, le, l, t < ntiles && t * 16 + col < E);
       }
-      const double v = wsum(log(lp) + (double)le * 0.69314718055994530942);
+      // all 64 lanes hold columns (4 tiles x 16), libm's log: not i8l_set_finish
+      const double v = wsum(log(lp) + (double)le * kLn2);
       if (lane == 0) partial[(size_t)b * nsets + set] = nullsum[set] + v;
     }
   }
@@ -1587,7 +1627,7 @@ __global__ __launch_bounds__(WAVES * kWave, NEMO_I8L2_OCC) void score_i8p_kernel
   // one evaluation buffer: G [SPAD] f64, gi [2][SPAD], perm [SPAD], A [NSL][SPAD][4] x 16 B
   constexpr int kBufG = 0, kBufGi = SPAD * 8, kBufPerm = kBufGi + 2 * SPAD * 4, kBufA = kBufPerm + SPAD * 4;
   constexpr int kBuf = kBufA + NSL * SPAD * 64;
-  static_assert(kBufA % 16 == 0 && kBuf % 16 == 0, "16-B alignment of the A fragments");
+  static_assert(kBuf == I8Lds<SPAD, NSL, 1, 2>::kBuf && kBufA == I8Lds<SPAD, NSL>::kA, "I8Lds describes it");
   extern __shared__ __attribute__((aligned(16))) double lds8[];
   uint2* etab_o = (uint2*)lds8;                          // [kExpTabN] at LDS address 0
   double2* ltab = (double2*)(etab_o + kExpTabN);         // [128] log table
@@ -1712,11 +1752,8 @@ hipError_t launch_i8s_t(Ctx& c, int batch, int cap, const int32_t* d_pos, const 
   constexpr int SPAD = NR * 16;
   const int ntiles = (c.E + 15) / 16;
   const int nsets = (ntiles + 7) / 8;
-  const int slots = 256 * (NEMO_I8O_WAVES_PER_SIMD * 4 / 8);
-  int split = (slots + batch - 1) / batch;
-  split = split < 1 ? 1 : (split > nsets ? nsets : split);
-  const size_t region = std::max((size_t)7 * SPAD * 64, (size_t)16384);
-  const size_t lds = kExpTabN * 8 + 128 * 16 + 3 * SPAD * 8 + 3 * SPAD * 4 + region;
+  const int split = i8_split(256 * (NEMO_I8O_WAVES_PER_SIMD * 4 / 8), batch, nsets);
+  const size_t lds = I8Lds<SPAD, 7>::bytes(kI8sColsum);
   score_i8s_kernel<NR><<<dim3(batch * split), 8 * kWave, lds, st>>>(
       c.S, c.E, ntiles, nsets, split, cap, c.i8o_padg, d_pos, d_w01, c.d_elo, c.d_ehi, c.d_B8,
       c.d_udig2, c.d_u0, c.d_nullsum, c.d_i8o_tabs, fpartial(c), d_ll, c.xcd_remap);
@@ -1731,7 +1768,7 @@ hipError_t launch_i8p_t(Ctx& c, int batch, int cap, const int32_t* d_pos, const 
   constexpr int SPAD = NR * 16;
   const int ntiles = (c.E + 15) / 16;
   const int nsets = (ntiles + 7) / 8;
-  const size_t lds = kExpTabN * 8 + 128 * 16 + 2 * SPAD * 8 + 2 * ((size_t)SPAD * 20 + (size_t)7 * SPAD * 64);
+  const size_t lds = I8Lds<SPAD, 7, 1, 2>::kBytes;
   int dev = 0, ncu = 0;
   hipError_t ge = hipGetDevice(&dev);
   if (ge == hipSuccess) ge = hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
@@ -1760,15 +1797,14 @@ hipError_t launch_i8p_t(Ctx& c, int batch, int cap, const int32_t* d_pos, const 
 template <int NR, int WAVES, int OCC = NEMO_I8O_WAVES_PER_SIMD, int TT = 1, bool SPLIT = false>
 hipError_t launch_i8l_t(Ctx& c, int batch, int cap, const int32_t* d_pos, const double* d_w01,
                         double* d_ll, hipStream_t st, int* nparts, bool* finalized) {
-  constexpr int SPAD = NR * 16;
+  using L = I8Lds<NR * 16, 7>;
   const int ntiles = (c.E + 15) / 16;
   const int nsets = (ntiles + 7) / 8;
-  const int slots = 256 * (OCC * 4 / WAVES);
-  int split = (slots + batch - 1) / batch;
-  split = split < 1 ? 1 : (split > nsets ? nsets : split);
-  const size_t lds = kExpTabN * 8 + 128 * 16 + 3 * SPAD * 8 + 3 * SPAD * 4 + (size_t)7 * SPAD * 64;
-  if (SPLIT) {  // a prep-only launch (one block per evaluation), then the walks
-    if (!c.d_i8img || c.i8img_cap < batch || (size_t)SPAD * 460 != i8img_bytes(c.fspad))
+  const int split = i8_split(256 * (OCC * 4 / WAVES), batch, nsets);
+  const size_t lds = L::bytes();
+  // the prep-only and walk-only kernels exist for the split row alone
+  if constexpr (SPLIT) {  // a prep-only launch (one block per evaluation), then the walks
+    if (!c.d_i8img || c.i8img_cap < batch || (size_t)L::kImg != i8img_bytes(c.fspad))
       return hipErrorInvalidValue;
     score_i8l_kernel<NR, WAVES, OCC, TT, 1><<<dim3(batch), WAVES * kWave, lds, st>>>(
         c.S, c.E, ntiles, nsets, 1, cap, c.i8o_padg, d_pos, d_w01, c.d_elo, c.d_ehi, c.d_B8,
@@ -1893,16 +1929,12 @@ __global__ __launch_bounds__(WAVES * kWave, OCC) void score_i8w_kernel(
     double* __restrict__ partial, double* __restrict__ ll_out, int remap) {
   constexpr int NR = 8, SPAD = NR * 16;
   constexpr int NSL = 7;
+  using L = I8Lds<SPAD, NSL, kWideKH>;
   extern __shared__ __attribute__((aligned(16))) double lds8[];
-  uint2* etab_o = (uint2*)lds8;                          // [kExpTabN] at LDS address 0
-  double2* ltab = (double2*)(etab_o + kExpTabN);         // [128] log table
-  double* elo_s = (double*)(ltab + 128);                 // [SPAD] e^lo_j
-  double* ehi_s = elo_s + SPAD;                          // [SPAD] e^hi_j
-  EvalLds ev;
-  ev.G = ehi_s + SPAD;                                   // [SPAD]
-  int* gi = (int*)(ev.G + SPAD);                         // [2][SPAD] g0, g1
-  ev.perm = gi + 2 * SPAD;                               // [SPAD]
-  ev.A = (i32x4*)(ev.perm + SPAD);                       // [NSL][KH][SPAD][4] swizzled (a_byte)
+  double2* ltab = L::ltab(lds8);
+  double *elo_s = L::elo(lds8), *ehi_s = L::ehi(lds8);
+  const EvalLds ev = L::eval(lds8);
+  int* gi = L::gi(lds8);
 
   const int b = xcd_index8((int)blockIdx.x, (int)gridDim.x, remap);
   const int tid = threadIdx.x;
@@ -1910,40 +1942,14 @@ __global__ __launch_bounds__(WAVES * kWave, OCC) void score_i8w_kernel(
   const int w = __builtin_amdgcn_readfirstlane(tid / kWave);
   const int col = lane & 15, rg = lane >> 4;
 
-  {  // both tables (precomputed per context) in one contiguous 18 KB copy
-    const int4* src = (const int4*)tabs;
-    int4* dst = (int4*)lds8;
-    for (int k = tid; k < (kExpTabN * 8 + 128 * 16) / 16; k += blockDim.x) dst[k] = src[k];
-    for (int i = tid; i < SPAD; i += blockDim.x) {
-      elo_s[i] = i < S ? e_lo[i] : 1.0;
-      ehi_s[i] = i < S ? e_hi[i] : 1.0;
-    }
-  }
+  i8_copy_tables<SPAD>(lds8, elo_s, ehi_s, tabs, e_lo, e_hi, S, tid, blockDim.x);
   i8_init_eval<SPAD, NSL * kWideKH, 4>(ev, pos + (size_t)b * S, S, tid, blockDim.x, padg);
   __syncthreads();
-  {  // U' / ln 2 as the free diagonal "parent" i of child i
-    int8_t* A8 = (int8_t*)ev.A;
-    for (int k = tid; k < S * NSL; k += blockDim.x) {
-      const int i = k / NSL, sl = k - i * NSL;
-      const int8_t d = udig[i * 8 + sl];
-      A8[(sl * kWideKH + (i >> 6)) * SPAD * 64 + a_byte<4>(i, i & 63)] = sl == 4 ? (int8_t)(2 * d) : d;
-    }
-  }
-  {
-    constexpr int KB = 2;
-    const int npass = i8_npass(S, cap);
-    const int my = npass > w ? (npass - w + WAVES - 1) / WAVES : 0;
-    for (int k0 = 0; k0 < my; k0 += KB)
-      i8w_prep_passes<WAVES, KB>(ev, k0, w, lane, S, cap, w01 + (size_t)b * S * S, elo_s, ehi_s, ltab);
-  }
+  i8l_diag<SPAD, kWideKH>(ev.A, udig, S, tid, blockDim.x);
+  for (int k0 = 0, my = i8_wave_passes<WAVES>(S, cap, w); k0 < my; k0 += 2)
+    i8w_prep_passes<WAVES, 2>(ev, k0, w, lane, S, cap, w01 + (size_t)b * S * S, elo_s, ehi_s, ltab);
   __syncthreads();
-  // G + u0 in units of 2^-20 / ln 2 (score_i8l_kernel)
-  for (int i = tid; i < SPAD; i += blockDim.x) {
-    const double g = i < S ? ev.G[i] + u0[i] : ev.G[i];
-    const double g0 = rint(g * kL2Scale);
-    gi[i] = (int)g0 + (1023 << 20);
-    gi[SPAD + i] = (int)rint(fma(g, kL2Scale, -g0) * 262144.0);
-  }
+  i8l_split_g<SPAD>(ev, gi, u0, S, tid, blockDim.x);
   __syncthreads();
 
   const i32x4* Gi = (const i32x4*)gi;
@@ -2054,12 +2060,8 @@ __global__ __launch_bounds__(WAVES * kWave, OCC) void score_i8w_kernel(
       const double l = rowsum_pair(la0 + la1, lb0 + lb1) + 1.0;  // + e^0 of the null row
       const bool tile_b = (lane & 16) != 0;
       const bool ok = (((tile_b ? tb : ta) * 16 + col) < E) & (two | !tile_b);
-      const double lprod = ok ? l : 1.0;  // one factor per lane: no renormalisation
-      // rows 0 / 1 hold tile a's / tile b's 16 column values
-      double v = log_fast(lprod, ltab);
-      v = rowsum16(v);
-      v += __shfl_down(v, 16, kWave);
-      if (lane == 0) partial[(size_t)b * nsets + set] = nullsum[set] + v;
+      // one factor per lane: no renormalisation, so i8l_set_store on its log
+      i8l_set_store<true>(log_fast(ok ? l : 1.0, ltab), lane, nullsum, partial, b, nsets, set);
     }
   } else {
     for (int set = w; set < nsets; set += WAVES) {
@@ -2092,32 +2094,28 @@ __global__ __launch_bounds__(WAVES * kWave, OCC) void score_i8w_kernel(
           l1 = __builtin_amdgcn_mfma_i32_16x16x64_i8(A(5, 1), b64[1], l1, 0, 0, 0);
           l1 = __builtin_amdgcn_mfma_i32_16x16x64_i8(A(6, 0), b1[0], l1, 0, 0, 0);
           l1 = __builtin_amdgcn_mfma_i32_16x16x64_i8(A(6, 1), b1[1], l1, 0, 0, 0);
+          // the log2 cell epilogue (see score_i8l_kernel's one-tile walk)
           uint32_t t0[4];
           uint64_t evv[4];
           double pr[4];
-  #pragma unroll
+#pragma unroll
           for (int g = 0; g < 4; ++g) {
+            // T_0 wraps mod 2^32 only transiently (its true value is in (0, 2^31))
             t0[g] = ((uint32_t)h0[g] << 12) + (uint32_t)h1[g];
             evv[g] = exp2_fx_load(t0[g]);
           }
-  #pragma unroll
+#pragma unroll
           for (int g = 0; g < 4; ++g)
             pr[g] = exp2_fx_series(t0[g], (int)(((uint32_t)l0[g] << 11) + (uint32_t)l1[g]));
-  #pragma unroll
+#pragma unroll
           for (int g = 0; g < 4; ++g) {
             if (g & 1) ls1 = exp2_fx_apply(t0[g], evv[g], pr[g], ls1);
             else ls0 = exp2_fx_apply(t0[g], evv[g], pr[g], ls0);
           }
         }
-        const double l = rowsum4(ls0 + ls1) + 1.0;  // + e^0 of the null row
-        lprod *= t * 16 + col < E ? l : 1.0;
-        lexp += __builtin_amdgcn_frexp_exp(lprod);
-        lprod = __builtin_amdgcn_frexp_mant(lprod);
+        i8_colprod(lprod, lexp, rowsum4(ls0 + ls1) + 1.0, t * 16 + col < E);  // + e^0 of the null row
       }
-      // every 16-lane row holds the 16 column products (rowsum4)
-      double v = log_fast(lprod, ltab) + (double)lexp * 0.69314718055994530942;
-      v = rowsum16(v);
-      if (lane == 0) partial[(size_t)b * nsets + set] = nullsum[set] + v;
+      i8l_set_finish<false>(lprod, lexp, ltab, lane, nullsum, partial, b, nsets, set);
     }
   }
   __syncthreads();
@@ -2187,7 +2185,7 @@ hipError_t launch_i8w_t(Ctx& c, int batch, int cap, const int32_t* d_pos, const 
   constexpr int SPAD = 128, WAVES = 16, NSL = 7;
   const int ntiles = (c.E + 15) / 16;
   const int nsets = (ntiles + kWideSetT - 1) / kWideSetT;
-  const size_t lds = kExpTabN * 8 + 128 * 16 + 3 * SPAD * 8 + 3 * SPAD * 4 + (size_t)NSL * kWideKH * SPAD * 64;
+  const size_t lds = I8Lds<SPAD, NSL, kWideKH>::bytes();
   hipError_t ae = hipFuncSetAttribute((const void*)score_i8w_kernel<WAVES, 4, TWO>,
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (ae != hipSuccess) return ae;
@@ -2358,7 +2356,6 @@ hipError_t stage_i8o(Ctx& c, const std::vector<double>& elo, const std::vector<d
       // and T_0 = (x / ln 2 + 1023) 2^20 must stay in (0, 2^31): |x| <= 690
       // (checked above) gives 27 < x / ln 2 + 1023 < 2019, and G + u0 rides
       // in T_0's C-init, so |G + u0| / ln 2 + 1023 < 2047
-      constexpr double kLn2 = 0.69314718055994530942;
       const double vmax = ldexp(1.0, 25) - ldexp(1.0, 17) - ldexp(1.0, 11) - 64.0;
       double dmax = 0.0, umax0 = 0.0;
       for (int j = 0; j < S; ++j) dmax = std::max(dmax, fabs(log(ehi[j]) - log(elo[j])));

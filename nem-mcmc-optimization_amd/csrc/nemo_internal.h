@@ -261,8 +261,11 @@ inline double* fpartial(const Ctx& c) { return c.part_out ? c.part_out : c.d_fpa
 
 // the split variant (FactKernel::split): bytes of one evaluation's prep image (G split [2][SPAD]
 // int, perm [SPAD] int, digits [7][SPAD][64] bytes) and its buffer for the
-// reserved batch (allocated when the option is set or the batch grows)
-inline size_t i8img_bytes(int spad) { return (size_t)spad * 460; }
+// reserved batch (allocated when the option is set or the batch grows).
+// Per padded row: gi 8 + perm 4 + 7 x 64 digit bytes; the kernels' LDS layout
+// (I8Lds, nemo_factored_i8.hip) asserts that it agrees.
+constexpr int kI8ImgRowBytes = 8 + 4 + 7 * 64;
+inline size_t i8img_bytes(int spad) { return (size_t)spad * kI8ImgRowBytes; }
 hipError_t i8img_reserve(Ctx& c);
 
 // ---- launchers (nemo_kernels.hip); all enqueue on `st` and never allocate ----

@@ -12,9 +12,11 @@ task=$1; shift
 # the same inputs, the fact_kernel variants' bits, then interleaved sweeps
 task_ab() (
 O=${AB_OUT:-gpurun_out/ab2}; mkdir -p $O; export PYTHONUNBUFFERED=1
-timeout -k 10 200 python tools/ab_bits_libs.py $O/new.npy > $O/bits_new.log 2>&1 || exit 1
-NEMO_LIBRARY=$(pwd)/nem-mcmc-optimization_amd/nemo/libnemo_old.so timeout -k 10 200 python tools/ab_bits_libs.py $O/old.npy > $O/bits_old.log 2>&1 || exit 1
-python -c "import numpy as np; a=np.load('$O/new.npy'); b=np.load('$O/old.npy'); print('bits equal:', np.array_equal(a,b), a.shape, 'max diff', np.max(np.abs(a-b)))"
+for B in ${AB_BITS_B:-257}; do   # (AB_BITS_B="257 1100": also with one block per evaluation)
+timeout -k 10 300 python tools/ab_bits_libs.py $O/new$B.npy $B > $O/bits_new$B.log 2>&1 || exit 1
+NEMO_LIBRARY=$(pwd)/nem-mcmc-optimization_amd/nemo/libnemo_old.so timeout -k 10 300 python tools/ab_bits_libs.py $O/old$B.npy $B > $O/bits_old$B.log 2>&1 || exit 1
+python -c "import numpy as np, sys; a=np.load('$O/new$B.npy'); b=np.load('$O/old$B.npy'); eq=np.array_equal(a,b); print('B=$B bits equal:', eq, a.shape, 'max diff', np.max(np.abs(a-b)), 'refused', int((a==-1.0e300).sum()) // $B); sys.exit(0 if eq else 1)" || exit 1
+done
 [ -n "$AB_SKIP_VARIANTS" ] || timeout -k 10 200 python tools/ab_bits.py 10 14 16 12 11 | grep -c True || exit 1
 ROUNDS=${ROUNDS:-3} AB_B=${AB_B:-512,2048} AB_OUT=$O bash tools/ab_libs.sh
 )
