@@ -12,7 +12,8 @@
 //    width ((mn / 2 + 1) / 2) * 2, the unblocked getf2 (lapack/getf2/getf2.c) once
 //    that width is <= 4 -- pivots of earlier columns, the strided ddot of the U part,
 //    dgemv_n of the rest, idamax (first largest |.|), the row swap and the scale by
-//    the pivot's reciprocal -- then per panel the row swaps (laswp), the unit lower
+//    the pivot's reciprocal (a non-zero pivot below DBL_MIN is only recorded:
+//    neither happens) -- then per panel the row swaps (laswp), the unit lower
 //    triangular solve (dtrsm_kernel_LT: row blocks of 16, then 8 / 4 / 2 / 1, each
 //    the GEMM chain of the solved rows above it, then in-block fma(-b, l, x)) and the
 //    trailing update (dgemm_kernel, alpha -1: rows in blocks of 16, 8, 4, 2, 1 and
@@ -32,10 +33,12 @@
 // n = 1..64 getri) and the device build is compared with scipy.linalg.inv by
 // tests/test_gpu_ancestor.py.
 //
-// Flags per chain (d_flag): 1 a zero pivot (scipy raises LinAlgError "singular
-// matrix"), 2 a non-finite entry of I - W~ (scipy's check_finite raises
-// ValueError), 4 a non-finite value in the factors or the inverse (the
-// restatement is not held to the library's bits there: the host recomputes).
+// Flags per chain (d_flag): 1 a zero pivot, or a zero left on U's diagonal by an
+// unswapped pivot below DBL_MIN (scipy raises LinAlgError "singular matrix",
+// from getrf's or getri's info), 2 a non-finite entry of I - W~ (scipy's
+// check_finite raises ValueError), 4 a non-finite value in the factors or the
+// inverse (the restatement is not held to the library's bits there: the host
+// recomputes).
 #include "nemo_internal.h"
 #include "refmath.h"
 
@@ -45,6 +48,7 @@ namespace {
 constexpr int kAncS = 64;   // one lane per row
 constexpr int kLd = 65;     // LDS column stride in doubles: a lane per column, distinct banks
 constexpr int kJb = 32;     // the widest panel of a getrf at S <= 64
+constexpr double kDblMin = 2.2250738585072014e-308;   // DBL_MIN: getf2's threshold for a usable pivot
 
 // One wave per chain; every phase is written for latency: the matrix lives in
 // LDS, but a phase's operands are loaded in batches ahead of its dependent
@@ -134,8 +138,9 @@ struct Lu {
 // rows & ~3 the 4-column kernel t = a1 x1, fma a0 x0, a2 x2, a3 x3, y = fma(t,
 // -1, y), a 2-column step, unfused y + a (x * -1) for the last column; the last
 // rows & 3 rows one fma chain, y = fma(t, -1, y)); idamax; the row swap and the
-// scale by the pivot's reciprocal.  Branch-free: every unrolled step computes
-// and a uniform select keeps it or not, so the loads issue ahead of the chains.
+// scale by the pivot's reciprocal, both only for |pivot| >= DBL_MIN.
+// Branch-free: every unrolled step computes and a uniform select keeps it or
+// not, so the loads issue ahead of the chains.
 template <int NM>
 __device__ __forceinline__ void lu_getf2(Lu& L, int off, int n) {
   NEMO_RM_NOCONTRACT
@@ -215,7 +220,9 @@ __device__ __forceinline__ void lu_getf2(Lu& L, int off, int n) {
     const int jp = col + (ix < kAncS ? ix : 0);
     const double t1 = readlane_d(bv, jp);
     if (lane == 0) L.piv[col] = jp + 1;
-    if (t1 != 0.0) {
+    if (t1 == 0.0) {
+      L.flag |= 1;
+    } else if (fabs(t1) >= kDblMin) {   // a pivot below DBL_MIN is recorded, not swapped in or scaled by
       if (jp != col) {
         const double vc = readlane_d(bv, col);
         bv = lane == col ? t1 : lane == jp ? vc : bv;
@@ -229,8 +236,6 @@ __device__ __forceinline__ void lu_getf2(Lu& L, int off, int n) {
       }
       const double r = 1.0 / t1;
       bv = (lane > col && lane < S) ? bv * r : bv;
-    } else {
-      L.flag |= 1;
     }
     if (lane >= off && lane < S) at(a, lane, col) = bv;
     __syncthreads();
@@ -546,6 +551,10 @@ __global__ __launch_bounds__(kAncS) void ancestor_kernel(int S_arg, int cap, con
 #endif
   if (all_finite) {
     lu_getrf<0>(L, 0, S);
+    // dtrtri's own check: a zero on U's diagonal that getrf did not report (left
+    // there by a pivot below DBL_MIN that was not swapped in) ends getri with
+    // info > 0, and scipy raises LinAlgError
+    if (__any(lane < S && at(a, lane, lane) == 0.0)) L.flag |= 1;
 #if NEMO_ANC_PROFILE
     tp[1] = clock64();
 #endif

@@ -3,9 +3,21 @@
 // on the host and compared bit for bit with the library itself (dlopen'ed):
 // the LU factors and pivots for n = 1..128, the inverse for n = 1..64 (the
 // device path's range).  Build with -ffp-contract=off: every fused operation
-// is an explicit fma().
+// is an explicit fma().  The inputs are I - W~ of a random order in seven value
+// modes of the trial index (mode = (trial / 2) % 8; odd trials add stale entries
+// outside the order's triangle, drawn as the mode draws, so some are singular:
+// getrf is compared on those too, getri only when info == 0):
+//   0 smooth (expit of uniform(-4, 4));  1 all-saturated (0, 1/2, 1, 1);
+//   2 all ones;  3 few distinct values (1/2, 1, 1/4);  4 expit of +-40 logits;
+//   5 subnormal, 1 - 2^-53 and 1;  6 smooth with stale entries of either sign
+//   up to 3 on every trial, and on odd trials a perturbed diagonal;  7 as 5, and
+//   the order's first node has a stale 1 on its diagonal entry and subnormal
+//   weights to all its children: its column's pivot is below DBL_MIN, which
+//   getf2 records but neither swaps in nor scales by (the row stays, the rest
+//   of the factorisation and dgetri's info follow from that).
 //   lapack_check <path to libscipy_openblas*.so> [trials]
 #include <dlfcn.h>
+#include <float.h>
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -79,7 +91,8 @@ static void getf2(int S, double* a, int lda, int* piv, int off, int n) {
         if (fabs(b[i]) > mx) { mx = fabs(b[i]); jp = i; }
       piv[off + jl] = off + jp + 1;
       double t1 = b[jp];
-      if (t1 != 0.0) {
+      // a pivot below DBL_MIN is recorded, but neither swapped in nor scaled by
+      if (t1 != 0.0 && fabs(t1) >= DBL_MIN) {
         if (jp != jl)
           for (int k = 0; k <= jl; ++k) { double t = A(off + jl, off + k); A(off + jl, off + k) = A(off + jp, off + k); A(off + jp, off + k) = t; }
         double r = 1.0 / t1;
@@ -178,6 +191,24 @@ static void getri(int n, double* a, int lda, const int* piv) {
 
 static double rnd(void) { return (double)rand() / RAND_MAX * 2 - 1; }
 
+enum { MODES = 8 };
+static const char* const mode_name[MODES] = {"smooth", "all-saturated", "all ones", "few distinct", "+-40 logits",
+                                             "subnormal and 1 - 2^-53", "signed stale > 1", "subnormal pivot"};
+
+// one W~ entry of the mode
+static double draw(int mode) {
+  static const double sat[4] = {0.0, 0.5, 1.0, 1.0}, few[3] = {0.5, 1.0, 0.25};
+  const double edge[6] = {0x1p-1074, exp(-720.0), exp(-709.0), 1.0 - 0x1p-53, 1.0, 0.7310585786300049};
+  switch (mode) {
+    case 1: return sat[rand() % 4];
+    case 2: return 1.0;
+    case 3: return few[rand() % 3];
+    case 4: return 1.0 / (1.0 + exp(-40 * rnd()));
+    case 5: case 7: return edge[rand() % 6];
+    default: return 1.0 / (1.0 + exp(-4 * rnd()));
+  }
+}
+
 int main(int argc, char** argv) {
   if (argc < 2) { fprintf(stderr, "usage: lapack_check <libscipy_openblas.so> [trials]\n"); return 2; }
   void* L = dlopen(argv[1], RTLD_NOW);
@@ -193,15 +224,20 @@ int main(int argc, char** argv) {
   for (int n = 1; n <= LD; ++n)
     for (int t = 0; t < trials; ++t) {
       // I - W~ of a random order (a DAG's strict triangle under a permutation),
-      // with stale entries elsewhere on odd trials
+      // with stale entries elsewhere on odd trials (mode 6: on every trial)
+      const int mode = (t / 2) % MODES;
       for (int i = 0; i < n * n; ++i) X[i] = 0.0;
       for (int i = 0; i < n; ++i)
         for (int k = 0; k < n; ++k) {
           if (i == k) continue;
           int pi = (i * 37 + t) % n, pk = (k * 37 + t) % n;   // a permutation when gcd(37, n) = 1
-          if (pk < pi || ((t & 1) && rand() % 7 == 0)) X[i + k * n] = -1.0 / (1.0 + exp(-4 * rnd()));
+          if (pk < pi) X[i + k * n] = (mode == 7 && pk == 0) ? -((rand() & 1) ? exp(-709.0) : exp(-720.0)) : -draw(mode);
+          else if (((t & 1) || mode == 6) && rand() % 7 == 0) X[i + k * n] = mode == 6 ? 3 * rnd() : -draw(mode);
         }
-      for (int i = 0; i < n; ++i) X[i + i * n] = 1.0;
+      for (int i = 0; i < n; ++i) X[i + i * n] = (mode == 6 && (t & 1)) ? 1.0 - 0.5 * rnd() : 1.0;
+      if (mode == 7)
+        for (int k = 0; k < n; ++k)
+          if ((k * 37 + t) % n == 0) X[k + k * n] = 0.0;
       memcpy(Y, X, sizeof(double) * n * n);
       int info;
       dgetrf(&n, &n, X, &n, p1, &info);
@@ -212,9 +248,12 @@ int main(int argc, char** argv) {
         int lwork = (int)(1.01 * 64 * n);
         dgetri(&n, X, &n, p1, W, &lwork, &info);
         getri(n, Y, n, p2);
-        for (int i = 0; i < n * n; ++i) bad += memcmp(&X[i], &Y[i], 8) != 0;
+        // info > 0: a zero on U's diagonal behind an unswapped subnormal pivot; dtrtri
+        // returns at once and scipy raises LinAlgError.  An overflowing inverse is compared too.
+        if (info == 0)
+          for (int i = 0; i < n * n; ++i) bad += memcmp(&X[i], &Y[i], 8) != 0;
       }
-      if (bad) { printf("n=%d trial %d: %d differing values\n", n, t, bad); return 1; }
+      if (bad) { printf("n=%d trial %d mode %d (%s): %d differing values\n", n, t, mode, mode_name[mode], bad); return 1; }
     }
   printf("ok\n");
   return 0;

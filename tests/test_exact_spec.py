@@ -78,7 +78,10 @@ def _scipy_openblas():
 def test_lapack_inverse_restatement_against_scipys_openblas(tmp_path):
     """tests/host/lapack_check.c: getrf (n = 1..128) and getri (n <= 64) as
     csrc/nemo_ancestor.hip restates them, against scipy's own LAPACK calls
-    (scipy_dgetrf_ / scipy_dgetri_, dlopen'ed), to the bit."""
+    (scipy_dgetrf_ / scipy_dgetri_, dlopen'ed), to the bit: 16 trials per n, so
+    each of its eight value modes (smooth, all-saturated, all ones, few distinct
+    values, +-40 logits, subnormal and 1 - 2^-53, signed stale entries past 1, a
+    pivot below DBL_MIN) runs without and with stale entries."""
     gcc = shutil.which("gcc")
     path, arch = _scipy_openblas()
     if gcc is None or path is None:
@@ -88,7 +91,7 @@ def test_lapack_inverse_restatement_against_scipys_openblas(tmp_path):
     exe = str(tmp_path / "lc")
     subprocess.run([gcc, "-O2", "-ffp-contract=off", os.path.join(HOST, "lapack_check.c"), "-ldl", "-lm",
                     "-o", exe], check=True)
-    r = subprocess.run([exe, path, "6"], capture_output=True, text=True)
+    r = subprocess.run([exe, path, "16"], capture_output=True, text=True)
     assert r.returncode == 0 and r.stdout.strip() == "ok", r.stdout + r.stderr
 
 
