@@ -118,6 +118,30 @@ int nemo_score(nemo_ctx* ctx, int batch, const int32_t* pos, const double* w01, 
 int nemo_score_dev(nemo_ctx* ctx, int batch, const int32_t* d_pos, const double* d_w01, int cap,
                    double* d_ll, double* d_cs, double* d_cells, double* d_ow, void* stream);
 
+/* ---- gradient of the order score in the mapped weights --------------------
+ * What NEMOrderMCMC.opt_weights / global_opt_fun (nem_order_mcmc.py:105-150)
+ * and the unused Jacobian of methods.py:84-104 were after; no reference
+ * counterpart runs, so the arithmetic is the fp64 fast arithmetic whatever
+ * "exact" / "exact_dev" / "fact_kernel" say.
+ *   ll_out   [batch]        as nemo_score
+ *   grad_out [batch][S][S]  d ll / d w01[i][j] = sum_e ow[i][e] (v - 1) /
+ *                           (1 - w + w v), v = exp(T[i][j][e]), at the
+ *                           permissible pairs; exactly 0.0 elsewhere (every
+ *                           entry is written; w01 is read only at those pairs)
+ * cap as for nemo_score.  NEMO_F64 contexts only (NEMO_F32: NEMO_ERR_ARG); a
+ * wide generic table is served (no products of exp(T) are taken).  A factored
+ * model with S <= 64 runs one fused MFMA kernel (the order weights never
+ * leave the registers), everything else two passes: the forward with order
+ * weights into the context's scratch, then a reduction (option "grad_path").
+ * Every sum has a fixed order that depends on the staged model alone: an
+ * evaluation's bits depend neither on the batch nor on its slot in it.
+ * _dev: enqueue only; after nemo_reserve(max_batch, .) with batch <=
+ * max_batch it neither allocates nor synchronises (else NEMO_ERR_STATE). */
+int nemo_score_grad(nemo_ctx* ctx, int batch, const int32_t* pos, const double* w01, int cap,
+                    double* ll_out, double* grad_out);
+int nemo_score_grad_dev(nemo_ctx* ctx, int batch, const int32_t* d_pos, const double* d_w01, int cap,
+                        double* d_ll, double* d_grad, void* stream);
+
 /* reuse-batched variant: `group` evaluations share every table row read
  * (group in {1,4,8,16}); same results as nemo_score_dev */
 int nemo_score_group_dev(nemo_ctx* ctx, int batch, int group, const int32_t* d_pos, const double* d_w01,
@@ -267,6 +291,11 @@ int nemo_inverse_sweep(nemo_ctx* ctx, int nprob, const int32_t* pos, const doubl
  *                prep-only one writing each evaluation's digits to HBM and a
  *                walk-only one reading them (10's bits; an experiment,
  *                measured slower)
+ *   "grad_path"  0 (default) auto: nemo_score_grad runs the fused kernel for a
+ *                factored model with S <= 64, else the two-pass path; 1 = the
+ *                two-pass path always (tests, A/B measurement)
+ *   "grad_path_used" (get only) the path the last nemo_score_grad(_dev) ran:
+ *                1 two-pass, 2 fused; 0 before any call
  *   "factored"   (get only) 1 if the staged table is factorable
  *   "win"        (get only) 1 if the capped lookup-table kernel is staged
  *                (U - U[S] two-valued per row, partial sums in range)

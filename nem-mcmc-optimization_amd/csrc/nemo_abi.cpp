@@ -187,7 +187,8 @@ void nemo_ctx_destroy(nemo_ctx* ctx) {
                   c.d_udig, c.d_udig2, c.d_u0, c.d_wuw, c.d_wnull, c.d_nullsum_w, c.d_i8img,
                   c.d_xlo,  c.d_xhi,  c.d_pwplan, c.d_xcs, c.d_xcells2, c.d_xcbuf,
                   c.d_xa,   c.d_xbits, c.d_pwpos, c.d_pwmeta, c.d_xtrace, c.d_xqueue,
-                  c.d_xcost, c.d_xorder, c.d_xhist, c.d_xsbuf, c.d_xX, c.d_xl};
+                  c.d_xcost, c.d_xorder, c.d_xhist, c.d_xsbuf, c.d_xX, c.d_xl,
+                  c.d_grad, c.d_gradM, c.d_gradll};
   for (void* p : bufs)
     if (p) (void)hipFree(p);
   for (int k = 0; k < Ctx::kStepSlots; ++k) {
@@ -230,6 +231,16 @@ int nemo_reserve(nemo_ctx* ctx, int max_batch, int max_chains) {
     HIPCHK(dalloc(&c.d_fG, nb * sp));
     HIPCHK(dalloc(&c.d_fperm, nb * sp));
     HIPCHK(dalloc(&c.d_fpartial, nb * (size_t)nemo::factored_partials(c)));
+    // nemo_score_grad: the host entry's gradient, and the fused kernel's parts
+    // (S <= 64, fp64: E alone fixes their count, so staging need not come first)
+    if (c.dtype == 0) {
+      HIPCHK(dalloc(&c.d_grad, nb * S * S));
+      if (nemo::grad_fused_shape(c)) {
+        const size_t np = (size_t)nemo::grad_parts(c.E);
+        HIPCHK(dalloc(&c.d_gradM, nb * np * nemo::grad_part_doubles((int)sp)));
+        HIPCHK(dalloc(&c.d_gradll, nb * np));
+      }
+    }
     c.cap_batch = nb;
     if (nemo::host::kFactKernels[c.fact_kernel].split) HIPCHK(nemo::i8img_reserve(c));
   }
@@ -801,6 +812,68 @@ int nemo_score(nemo_ctx* ctx, int batch, const int32_t* pos, const double* w01, 
   }
   HIPCHK(hipStreamSynchronize(st));
   c.ow_chains = 0;  // d_ow no longer holds fused-step order weights
+  return NEMO_OK;
+}
+
+// ---- d ll / d w01 (nemo_grad.hip) ----
+int nemo_score_grad_dev(nemo_ctx* ctx, int batch, const int32_t* d_pos, const double* d_w01, int cap,
+                        double* d_ll, double* d_grad, void* stream) {
+  int rc = check_ctx(ctx, true);
+  if (rc) return rc;
+  Ctx& c = ctx->c;
+  if (c.dtype != NEMO_F64)
+    return fail(NEMO_ERR_ARG, "nemo_score_grad: dtype f32 (NEMO_F32) context; the gradient is fp64 only (NEMO_F64)");
+  if (batch < 0 || cap < 0) return fail(NEMO_ERR_ARG, "batch=%d cap=%d", batch, cap);
+  if (batch == 0) return NEMO_OK;
+  if (batch > c.cap_batch) return fail(NEMO_ERR_STATE, "batch %d > reserved %d", batch, c.cap_batch);
+  if (!d_pos || !d_w01 || !d_ll || !d_grad) return fail(NEMO_ERR_ARG, "null device pointer");
+  if (c.score_path == 2 && !c.factored)
+    return fail(NEMO_ERR_STATE, "score_path=2 (factored) but the staged table is not factorable");
+  hipStream_t st = pick(ctx, stream);
+  const bool fact = use_factored(c);
+  if (fact && c.fspad <= 64 && c.grad_path != 1) {
+    HIPCHK(nemo::launch_score_grad_fused(c, batch, cap, d_pos, d_w01, d_ll, d_grad, st));
+    c.grad_path_used = 2;
+    return NEMO_OK;
+  }
+  // two passes: the forward with order weights into the context's d_ow (the
+  // chunked fp64 kernel, or the streaming one), then the reduction
+  if (fact) {
+    const int fk = c.fact_kernel;
+    c.fact_kernel = 1;  // option fact_kernel does not route this call
+    const hipError_t e = nemo::launch_score_factored(c, batch, cap, d_pos, d_w01, d_ll, nullptr, nullptr, c.d_ow, st);
+    c.fact_kernel = fk;
+    HIPCHK(e);
+  } else {
+    HIPCHK(nemo::launch_prep(c, batch, cap, d_pos, d_w01, c.d_rows, c.d_sw, c.d_cnt, nullptr, st));
+    HIPCHK(nemo::launch_score(c, batch, c.d_rows, c.d_sw, c.d_cnt, d_ll, nullptr, nullptr, c.d_ow, st));
+  }
+  c.ow_chains = 0;  // d_ow no longer holds fused-step order weights
+  HIPCHK(nemo::launch_grad_reduce(c, batch, cap, fact, d_pos, d_w01, c.d_ow, d_grad, st));
+  c.grad_path_used = 1;
+  return NEMO_OK;
+}
+
+int nemo_score_grad(nemo_ctx* ctx, int batch, const int32_t* pos, const double* w01, int cap, double* ll_out,
+                    double* grad_out) {
+  int rc = check_ctx(ctx, true);
+  if (rc) return rc;
+  Ctx& c = ctx->c;
+  if (c.dtype != NEMO_F64)
+    return fail(NEMO_ERR_ARG, "nemo_score_grad: dtype f32 (NEMO_F32) context; the gradient is fp64 only (NEMO_F64)");
+  if (batch < 0 || cap < 0) return fail(NEMO_ERR_ARG, "batch=%d cap=%d", batch, cap);
+  if (batch == 0) return NEMO_OK;
+  if (!pos || !w01 || !ll_out || !grad_out) return fail(NEMO_ERR_ARG, "null host pointer");
+  if ((rc = check_pos(pos, batch, c.S))) return rc;
+  if ((rc = nemo_reserve(ctx, batch, 0))) return rc;
+  const size_t S = c.S;
+  hipStream_t st = c.stream;
+  HIPCHK(hipMemcpyAsync(c.d_pos, pos, batch * S * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(c.d_w01, w01, batch * S * S * 8, hipMemcpyHostToDevice, st));
+  if ((rc = nemo_score_grad_dev(ctx, batch, c.d_pos, c.d_w01, cap, c.d_ll, c.d_grad, st))) return rc;
+  HIPCHK(hipMemcpyAsync(ll_out, c.d_ll, batch * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(grad_out, c.d_grad, batch * S * S * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
   return NEMO_OK;
 }
 
@@ -1691,6 +1764,11 @@ int nemo_set_option(nemo_ctx* ctx, const char* name, int value) {
     ctx->c.local_split = value;
     return NEMO_OK;
   }
+  if (strcmp(name, "grad_path") == 0) {
+    if (value < 0 || value > 1) return fail(NEMO_ERR_ARG, "grad_path=%d not in {0,1}", value);
+    ctx->c.grad_path = value;
+    return NEMO_OK;
+  }
   if (strcmp(name, "score_path") == 0) {
     if (value < 0 || value > 2) return fail(NEMO_ERR_ARG, "score_path=%d not in {0,1,2}", value);
     ctx->c.score_path = value;
@@ -1706,6 +1784,8 @@ int nemo_get_option(nemo_ctx* ctx, const char* name, int* value) {
   const Ctx& c = ctx->c;
   if (strcmp(name, "xcd_remap") == 0) *value = c.xcd_remap;
   else if (strcmp(name, "score_path") == 0) *value = c.score_path;
+  else if (strcmp(name, "grad_path") == 0) *value = c.grad_path;
+  else if (strcmp(name, "grad_path_used") == 0) *value = c.grad_path_used;
   else if (strcmp(name, "factored") == 0) *value = c.factored ? 1 : 0;
   else if (strcmp(name, "fact_kernel") == 0) *value = c.fact_kernel;
   else if (strcmp(name, "i8o") == 0) *value = c.i8o_ok ? (c.i8o_diag ? 2 : 1) : 0;

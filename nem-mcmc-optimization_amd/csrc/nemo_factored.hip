@@ -40,47 +40,6 @@ __device__ __forceinline__ double fwave_sum(double v) {
   return v;
 }
 
-// exp(x) for x <= ~0 in fp64 from a 64-entry table of 2^(j/64) and a
-// degree-5 polynomial on |r| <= ln2/128 (truncation < 4e-17): ~12 VALU ops
-// instead of the ~25 of the general exp; relative error a few ulp.
-__device__ __forceinline__ double exp_tab(double x, const double* __restrict__ tab) {
-  constexpr double kInvLn2x64 = 92.332482616893656768;     // 64 / ln 2
-  constexpr double kLn2d64Hi = 1.0830424696223417e-02;     // ln2/64, high part
-  constexpr double kLn2d64Lo = 2.5728046223276690e-14;     // ln2/64 - high part
-  x = fmax(x, -1000.0);
-  const double kf = rint(x * kInvLn2x64);
-  const int k = (int)kf;
-  double r = fma(-kf, kLn2d64Hi, x);
-  r = fma(-kf, kLn2d64Lo, r);
-  double p = fma(r, 1.0 / 120.0, 1.0 / 24.0);
-  p = fma(r, p, 1.0 / 6.0);
-  p = fma(r, p, 0.5);
-  p = fma(r, p, 1.0);
-  p = fma(r, p, 1.0);
-  return ldexp(p * tab[k & 63], k >> 6);
-}
-
-// exp(x) for finite x in [-1e12, ~0] (the log-sum-exp terms): 256-entry
-// table of 2^(j/256) and a degree-4 polynomial on |r| <= ln2/512 (truncation
-// < 4e-17).  k = round(x * 256/ln2) comes from the low word of
-// fma(x, 256/ln2, 1.5*2^52) (no clamp, rint or cvt), and the reduction uses
-// one constant: its error, |x| * 1.6e-16 relative, is weighted by e^x in the
-// sum (< 1e-16 of it).  9 f64 VALU + 3 integer.
-__device__ __forceinline__ double exp_lse(double x, const double* __restrict__ tab) {
-  constexpr double kInvLn2x256 = 369.32993046757462707;  // 256 / ln 2
-  constexpr double kLn2d256 = 2.7076061740622862e-03;    // ln 2 / 256
-  constexpr double kMagic = 6755399441055744.0;          // 1.5 * 2^52
-  const double t = fma(x, kInvLn2x256, kMagic);
-  const double kf = t - kMagic;
-  const int k = (int)(uint32_t)__builtin_bit_cast(uint64_t, t);
-  const double r = fma(-kf, kLn2d256, x);
-  double p = fma(r, 1.0 / 24.0, 1.0 / 6.0);
-  p = fma(r, p, 0.5);
-  p = fma(r, p, 1.0);
-  p = fma(r, p, 1.0);
-  return ldexp(p * tab[k & 255], k >> 8);
-}
-
 // v_max_f64 without the sNaN canonicalisation hipcc wraps around fmax: the
 // operands here are MFMA results and loads of finite tables
 __device__ __forceinline__ double vmax(double a, double b) {
@@ -88,10 +47,6 @@ __device__ __forceinline__ double vmax(double a, double b) {
   asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
   return r;
 }
-
-// value of the G column on padding rows (q >= S): cells of padding rows are
-// U[S][e] + kPadG, whose exp underflows to exactly 0 next to any real row
-constexpr double kPadG = -1.0e6;
 
 __device__ __forceinline__ int fxcd_work_index(int L, int N, int remap) {
   if (!remap) return L;
@@ -572,6 +527,14 @@ int resolve_fact_kernel(const Ctx& c, int cap, bool ll_only, double* bound) {
   return ch.fk;
 }
 
+hipError_t launch_prep_factored(Ctx& c, int batch, int cap, const int32_t* d_pos, const double* d_w01,
+                                hipStream_t st) {
+  const int spad = c.fspad;
+  prep_factored_kernel<<<batch * (spad / 4), 256, 0, st>>>(c.S, spad, cap, d_pos, d_w01, c.d_elo, c.d_ehi,
+                                                           c.d_fDp, c.d_fG, c.d_fperm);
+  return hipGetLastError();
+}
+
 hipError_t launch_score_factored(Ctx& c, int batch, int cap, const int32_t* d_pos,
                                  const double* d_w01, double* d_ll, double* d_cs, double* d_cells,
                                  double* d_ow, hipStream_t st, bool prepped, int* defer_np) {
@@ -587,11 +550,8 @@ hipError_t launch_score_factored(Ctx& c, int batch, int cap, const int32_t* d_po
   const int np_pred = host::fact_partials(k, c.E, c.nwords);
   if (np_pred > factored_partials(c)) return hipErrorInvalidValue;
   hipError_t err = hipSuccess;
-  if (!k.self_prep && !prepped) {  // the int8 and lookup-table kernels derive their inputs themselves
-    prep_factored_kernel<<<batch * (spad / 4), 256, 0, st>>>(c.S, spad, cap, d_pos, d_w01, c.d_elo,
-                                                             c.d_ehi, c.d_fDp, c.d_fG, c.d_fperm);
-    err = hipGetLastError();
-  }
+  if (!k.self_prep && !prepped)  // the int8 and lookup-table kernels derive their inputs themselves
+    err = launch_prep_factored(c, batch, cap, d_pos, d_w01, st);
   if (err != hipSuccess) return err;
   hipEvent_t e0 = nullptr, e1 = nullptr;
   if (c.timing && c.timing_kernel == 0 && c.ev_used + 2 <= c.ev_pool.size()) {

@@ -1,0 +1,357 @@
+// nemo_grad.hip -- gradient of the order score in the mapped parent weights.
+//
+// With cell[i][e] = U[i][e] + sum_{j in pa(i)} log(1 - w_ij + w_ij v_ij(e)),
+// v = e^T, and ll = sum_e logsumexp_i cell[i][e] (null row included),
+//     d ll / d w_ij = sum_e ow[i][e] f'_ij(e),
+//     f'_ij(e) = (v - 1) / fma(w_ij, v, 1 - w_ij),   ow = exp(cell - cs),
+// at the permissible pairs (pos[j] < pos[i], within the cap) and 0 elsewhere.
+// The denominator is the forward's own factor (delta_row, score_kernel).
+//
+// Factored model (nemo_factored.hip): v takes two values per parent row, by
+// the bit D1[j][e], so with M[i][j] = sum_e ow[i][e] D1[j][e] and the row sum
+// R[i] = sum_e ow[i][e]
+//     g_ij = f'_lo (R_i - M_ij) + f'_hi M_ij.
+// M = OW . D1^T is an (S x E) . (E x S) product with K = E: the transpose of
+// the forward's contraction.
+//
+// Fused kernel (S <= 64).  The forward runs TRANSPOSED on the fp64 matrix
+// cores: cells^T[e][q] = sum_p D1^T[e][p] Delta^T[p][q] -- the forward's own
+// two fragments with the MFMA operands swapped.  In the 16x16x4 C layout (col
+// = lane & 15, row = (lane >> 4) + 4 reg) register g of row block r then holds
+// the cell of child position q = 16 r + (lane & 15) at the tile's effect
+// 4 g + (lane >> 4), and after the column log-sum-exp (now a sum over the 16
+// lanes of a row and the row blocks) the order weight ow[q][e] there: exactly
+// the B fragment of k-step g of M^T[p][q] += sum_e D1[p][e] ow[q][e], whose A
+// fragment is the bit D1[p = 16 rp + (lane & 15)][e = 4 g + (lane >> 4)].  No
+// order weight crosses lanes, the LDS or HBM.  Only the tiles with p-block <=
+// q-block hold permissible pairs: NR (NR + 1) / 2 accumulator tiles (10 at
+// S = 64), and as many MFMAs per 16-effect tile as the forward.  Row p = 16 r
+// + 15 of the diagonal tile (r, r) is never a parent of its columns, so A = 1
+// there and the tile's row 15 is R[q].
+//
+// Every sum runs in a fixed order, with no atomics: a wave folds its tiles
+// (t_begin + w, + kGradWaves, ...) into its accumulators, the block adds its
+// waves' accumulators in wave order through the LDS, and grad_finish_kernel
+// adds the parts in order.  The parts are a function of E alone (grad_parts).
+#include "nemo_internal.h"
+
+#include <math.h>
+
+namespace nemo {
+
+namespace {
+
+using f64x4 = __attribute__((ext_vector_type(4))) double;
+
+__device__ __forceinline__ double gwave_sum(double v) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, kWave);
+  return v;
+}
+
+// max over each 16-lane row, in every lane of the row (rowsum16's moves)
+__device__ __forceinline__ double rowmax16(double v) {
+  v = fmax(v, dpp_d<0xB1>(v));
+  v = fmax(v, dpp_d<0x4E>(v));
+  v = fmax(v, dpp_d<0x141>(v));
+  v = fmax(v, dpp_d<0x140>(v));
+  return v;
+}
+
+__device__ __forceinline__ int gxcd_work_index(int L, int N, int remap) {
+  if (!remap) return L;
+  const int x = L & 7, k = L >> 3;
+  const int q = N >> 3, r = N & 7;
+  return x * q + (x < r ? x : r) + k;
+}
+
+// f' of one value v = e^t of a pair's table row at weight w
+__device__ __forceinline__ double fprime(double w, double v) { return (v - 1.0) / fma(w, v, 1.0 - w); }
+
+// position of a node in the order, clamped as the prep kernels clamp it
+__device__ __forceinline__ int clamp_pos(int p, int S) { return p < 0 ? 0 : (p >= S ? S - 1 : p); }
+
+// ---------------------------------------------------------------------------
+// fused: grid = batch * nparts (evaluation-major, XCD remap), block =
+// kGradWaves waves.  Mpart [b][part][tile (rq, rp), rq (rq + 1) / 2 + rp][reg][lane],
+// llpart [b][part].
+// ---------------------------------------------------------------------------
+template <int NR>
+__global__ __launch_bounds__(kGradWaves* kWave) void score_grad_fused_kernel(
+    int S, int E, int ntiles, int nparts, const double* __restrict__ Dp, const int32_t* __restrict__ permo,
+    const uint64_t* __restrict__ D1w, int nwords, const double* __restrict__ U, double* __restrict__ Mpart,
+    double* __restrict__ llpart, int remap) {
+  constexpr int SPAD = NR * 16;
+  constexpr int LDA = SPAD + 2;  // == 2 mod 32: conflict-free b64 Delta fragments
+  constexpr int NS = SPAD / 4;
+  constexpr int NT = NR * (NR + 1) / 2;
+  constexpr int TPB = kGradWaves * kGradTilesPerWave;
+  constexpr int NWB = TPB * 16 / 64;  // D1 words per parent row of a part (parts start on a word)
+  static_assert(SPAD * LDA >= NT * 256, "the wave reduction reuses Delta's LDS");
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+  double* etab = lds;                              // [256] 2^(j/256)
+  double2* ltab = (double2*)(etab + 256);          // [128] log_fast's table
+  double* llw = (double*)(ltab + 128);             // [kGradWaves]
+  double* A = llw + kGradWaves;                    // [SPAD][LDA], then the reduction's [NT][4][64]
+  uint64_t* words = (uint64_t*)(A + SPAD * LDA);   // [NWB][SPAD] D1 words, word-major
+
+  const int work = gxcd_work_index((int)blockIdx.x, (int)gridDim.x, remap);
+  const int b = work / nparts;
+  const int part = work - b * nparts;
+  const int t_begin = part * TPB;
+  const int t_end = min(ntiles, t_begin + TPB);
+  const int w_lo = part * NWB;
+  const int tid = threadIdx.x;
+  const int lane = tid & (kWave - 1);
+  const int w = __builtin_amdgcn_readfirstlane(tid / kWave);
+  const int col = lane & 15, rg = lane >> 4;
+
+  const int32_t* pm = permo + (size_t)b * SPAD;
+  if (tid < 256) etab[tid] = exp2((double)tid * (1.0 / 256.0));
+  fill_log_table(ltab, tid, blockDim.x);
+  for (int k = tid; k < SPAD * NWB; k += blockDim.x) {
+    const int u = k / SPAD, p = k - u * SPAD;
+    const int node = pm[p];
+    const int wi = w_lo + u;
+    words[k] = (node < S && wi < nwords) ? D1w[(size_t)node * nwords + wi] : 0ull;
+  }
+  const double* Db = Dp + (size_t)b * SPAD * SPAD;
+  for (int k = tid; k < SPAD * SPAD; k += blockDim.x) {
+    const int row = k / SPAD, kk = k - row * SPAD;
+    if (kk <= (row | 15)) A[row * LDA + kk] = Db[k];
+  }
+  // rows of U of this lane's NR child positions (S = the null row: padding)
+  // (element offsets: (S + 1) E < 2^31 for S <= 64 at every E the staging takes)
+  uint32_t urow[NR];
+#pragma unroll
+  for (int r = 0; r < NR; ++r) urow[r] = (uint32_t)pm[16 * r + col] * (uint32_t)E;
+  __syncthreads();
+
+  f64x4 acc2[NT];
+#pragma unroll
+  for (int k = 0; k < NT; ++k) acc2[k] = f64x4{0.0, 0.0, 0.0, 0.0};
+  double csum = 0.0;
+  const uint32_t diag = lane >= 48 ? 1u : 0u;
+
+  for (int t = t_begin + w; t < t_end; t += kGradWaves) {
+    // ---- cells^T of tile t: acc[r][g] = cell[q = 16 r + col][e = 16 t + 4 g + rg]
+    f64x4 acc[NR];
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const int ec = min(t * 16 + 4 * g + rg, E - 1);
+#pragma unroll
+      for (int r = 0; r < NR; ++r) acc[r][g] = U[urow[r] + ec];
+    }
+    const int uidx = ((t * 16) >> 6) - w_lo;
+    const int bit0 = (t * 16) & 63;
+    const uint64_t* wt = words + (size_t)uidx * SPAD;
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+      const uint32_t bv = (uint32_t)((wt[4 * s + rg] >> (bit0 + col)) & 1ull);
+#pragma unroll
+      for (int r = 0; r < NR; ++r) {
+        if (4 * s <= 16 * r + 12) {
+          // column 16 r + 15 of Delta's row block r holds G: the bit is 1 there
+          const uint32_t bb = (4 * s == 16 * r + 12) ? (bv | diag) : bv;
+          const double d = A[(16 * r + col) * LDA + 4 * s + rg];
+          acc[r] = __builtin_amdgcn_mfma_f64_16x16x4f64((double)bb, d, acc[r], 0, 0, 0);
+        }
+      }
+    }
+    // the D1 bits of the second contraction's A fragments: bit 4 g of pb[rp] is
+    // D1[p = 16 rp + col][effect 4 g + rg]
+    uint32_t pb[NR];
+#pragma unroll
+    for (int rp = 0; rp < NR; ++rp) pb[rp] = (uint32_t)(wt[16 * rp + col] >> (bit0 + rg));
+    // ---- per k-step g (the lane's effect 4 g + rg): the log-sum-exp over the
+    // children, the order weights, then M^T[p][q] += D1[p][e] ow[q][e]
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const int e = t * 16 + 4 * g + rg;
+      const bool valid = e < E;
+      const double unull = U[(size_t)S * E + (valid ? e : E - 1)];
+      double m = acc[0][g];
+#pragma unroll
+      for (int r = 1; r < NR; ++r) m = fmax(m, acc[r][g]);
+      m = fmax(rowmax16(m), unull);
+      double l = 0.0;
+#pragma unroll
+      for (int r = 0; r < NR; ++r) l += exp_lse(acc[r][g] - m, etab);
+      l = rowsum16(l) + exp_lse(unull - m, etab);
+      const double cs = m + log_fast(l, ltab);  // l in [1, SPAD + 1]
+      if (valid && col == 0) csum += cs;
+      double ow[NR];
+#pragma unroll
+      for (int r = 0; r < NR; ++r) ow[r] = valid ? exp_lse(acc[r][g] - cs, etab) : 0.0;
+#pragma unroll
+      for (int rp = 0; rp < NR; ++rp) {
+        const uint32_t av = (pb[rp] >> (4 * g)) & 1u;
+#pragma unroll
+        for (int rq = rp; rq < NR; ++rq) {
+          // row 16 r + 15 of the diagonal tile: never a parent there, A = 1 makes it R[q]
+          const uint32_t aa = (rq == rp && col == 15) ? 1u : av;
+          acc2[rq * (rq + 1) / 2 + rp] =
+              __builtin_amdgcn_mfma_f64_16x16x4f64((double)aa, ow[rq], acc2[rq * (rq + 1) / 2 + rp], 0, 0, 0);
+        }
+      }
+    }
+  }
+
+  // ---- the block's sums, waves in order (A's LDS reused once every wave is done with it)
+  csum = gwave_sum(csum);
+  if (lane == 0) llw[w] = csum;
+  double* red = A;
+  for (int ww = 0; ww < kGradWaves; ++ww) {
+    __syncthreads();
+    if (w == ww) {
+#pragma unroll
+      for (int k = 0; k < NT; ++k)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          const int idx = (k * 4 + g) * kWave + lane;
+          red[idx] = ww == 0 ? acc2[k][g] : red[idx] + acc2[k][g];
+        }
+    }
+  }
+  __syncthreads();
+  double* out = Mpart + ((size_t)b * nparts + part) * (NT * 256);
+  for (int k = tid; k < NT * 256; k += blockDim.x) out[k] = red[k];
+  if (tid == 0) {
+    double s = 0.0;
+    for (int ww = 0; ww < kGradWaves; ++ww) s += llw[ww];
+    llpart[(size_t)b * nparts + part] = s;
+  }
+}
+
+// grid = batch * ceil(S S / 256), block = 256: one entry of grad per thread
+// (every entry is written) and, in an evaluation's first block, its ll; the
+// parts are added in part order
+__global__ __launch_bounds__(256) void grad_finish_kernel(
+    int S, int SPAD, int cap, int nparts, const int32_t* __restrict__ pos, const double* __restrict__ w01,
+    const double* __restrict__ e_lo, const double* __restrict__ e_hi, const double* __restrict__ Mpart,
+    const double* __restrict__ llpart, double* __restrict__ ll, double* __restrict__ grad) {
+  const int nblk = (S * S + 255) / 256;
+  const int b = blockIdx.x / nblk, blk = blockIdx.x - b * nblk, tid = threadIdx.x;
+  const int nr = SPAD / 16;
+  const size_t pd = (size_t)nr * (nr + 1) / 2 * 256;
+  const double* Mb = Mpart + (size_t)b * nparts * pd;
+  if (blk == 0 && tid < kWave) {
+    const double s = sum_partials(llpart + (size_t)b * nparts, nparts, tid);
+    if (tid == 0) ll[b] = s;
+  }
+  const int32_t* pb = pos + (size_t)b * S;
+  const int k = blk * 256 + tid;
+  if (k < S * S) {
+    const int i = k / S, j = k - i * S;
+    const int q = clamp_pos(pb[i], S), p = clamp_pos(pb[j], S);
+    double g = 0.0;
+    if (p < q && (cap == 0 || q - p <= cap)) {
+      const int rq = q >> 4, rp = p >> 4, c = q & 15, row = p & 15;
+      const size_t om = (size_t)(rq * (rq + 1) / 2 + rp) * 256 + (row >> 2) * kWave + (row & 3) * 16 + c;
+      const size_t orr = (size_t)(rq * (rq + 1) / 2 + rq) * 256 + 3 * kWave + 48 + c;
+      double m = 0.0, r = 0.0;
+      for (int t = 0; t < nparts; ++t) {
+        m += Mb[t * pd + om];
+        r += Mb[t * pd + orr];
+      }
+      const double w = w01[(size_t)b * S * S + k];
+      g = fprime(w, e_lo[j]) * (r - m) + fprime(w, e_hi[j]) * m;
+    }
+    grad[(size_t)b * S * S + k] = g;
+  }
+}
+
+// ---------------------------------------------------------------------------
+// two-pass: grid = batch * S (one child per block), one wave per parent in
+// turn; lane sums over e = lane, lane + 64, ... then the xor tree
+// ---------------------------------------------------------------------------
+template <bool FACT>
+__global__ __launch_bounds__(256) void grad_reduce_kernel(
+    int S, int E, int cap, const int32_t* __restrict__ pos, const double* __restrict__ w01,
+    const double* __restrict__ ow, const uint64_t* __restrict__ D1w, int nwords, const double* __restrict__ e_lo,
+    const double* __restrict__ e_hi, const double* __restrict__ eT, double* __restrict__ grad) {
+  const int b = blockIdx.x / S, i = blockIdx.x - b * S;
+  const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
+  const int32_t* pb = pos + (size_t)b * S;
+  const int q = clamp_pos(pb[i], S);
+  const double* orow = ow + ((size_t)b * (S + 1) + i) * E;
+  for (int j = wv; j < S; j += 4) {
+    const int p = clamp_pos(pb[j], S);
+    const size_t k = ((size_t)b * S + i) * S + j;
+    if (!(p < q && (cap == 0 || q - p <= cap))) {
+      if (lane == 0) grad[k] = 0.0;
+      continue;
+    }
+    const double w = w01[k];
+    double g;
+    if (FACT) {
+      const uint64_t* bits = D1w + (size_t)j * nwords;
+      double s_lo = 0.0, s_hi = 0.0;
+      for (int e = lane; e < E; e += kWave) {
+        const double o = orow[e];
+        const bool hi = (bits[e >> 6] >> lane) & 1ull;
+        s_hi += hi ? o : 0.0;
+        s_lo += hi ? 0.0 : o;
+      }
+      g = fprime(w, e_lo[j]) * gwave_sum(s_lo) + fprime(w, e_hi[j]) * gwave_sum(s_hi);
+    } else {
+      const double* vrow = eT + ((size_t)i * S + j) * E;
+      const double s1 = 1.0 - w;
+      double s = 0.0;
+      for (int e = lane; e < E; e += kWave) {
+        const double v = vrow[e];
+        s += orow[e] * ((v - 1.0) / fma(w, v, s1));
+      }
+      g = gwave_sum(s);
+    }
+    if (lane == 0) grad[k] = g;
+  }
+}
+
+template <int NR>
+hipError_t launch_fused_t(Ctx& c, int batch, hipStream_t st) {
+  constexpr int SPAD = NR * 16;
+  const int ntiles = (c.E + 15) / 16;
+  const int nparts = grad_parts(c.E);
+  const size_t lds = (256 + 2 * 128 + kGradWaves) * 8 + (size_t)SPAD * (SPAD + 2) * 8 +
+                     (size_t)(kGradWaves * kGradTilesPerWave / 4) * SPAD * 8;
+  score_grad_fused_kernel<NR><<<dim3(batch * nparts), kGradWaves * kWave, lds, st>>>(
+      c.S, c.E, ntiles, nparts, c.d_fDp, c.d_fperm, c.d_D1w, c.nwords, (const double*)c.d_U64, c.d_gradM,
+      c.d_gradll, c.xcd_remap);
+  return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launch_score_grad_fused(Ctx& c, int batch, int cap, const int32_t* d_pos, const double* d_w01,
+                                   double* d_ll, double* d_grad, hipStream_t st) {
+  if (!c.factored || c.fspad > 64 || !c.d_gradM || !c.d_gradll) return hipErrorInvalidValue;
+  if (cap >= c.S - 1) cap = 0;  // a cap that cuts nothing (same lists, same bits)
+  hipError_t err = launch_prep_factored(c, batch, cap, d_pos, d_w01, st);
+  if (err != hipSuccess) return err;
+  switch (c.fspad / 16) {
+    case 1: err = launch_fused_t<1>(c, batch, st); break;
+    case 2: err = launch_fused_t<2>(c, batch, st); break;
+    case 4: err = launch_fused_t<4>(c, batch, st); break;
+    default: return hipErrorInvalidValue;
+  }
+  if (err != hipSuccess) return err;
+  grad_finish_kernel<<<batch * ((c.S * c.S + 255) / 256), 256, 0, st>>>(c.S, c.fspad, cap, grad_parts(c.E), d_pos, d_w01, c.d_elo, c.d_ehi,
+                                            c.d_gradM, c.d_gradll, d_ll, d_grad);
+  return hipGetLastError();
+}
+
+hipError_t launch_grad_reduce(Ctx& c, int batch, int cap, bool factored, const int32_t* d_pos,
+                              const double* d_w01, const double* d_ow, double* d_grad, hipStream_t st) {
+  if (c.dtype != 0) return hipErrorInvalidValue;
+  if (cap >= c.S - 1) cap = 0;
+  if (factored)
+    grad_reduce_kernel<true><<<batch * c.S, 256, 0, st>>>(c.S, c.E, cap, d_pos, d_w01, d_ow, c.d_D1w, c.nwords,
+                                                          c.d_elo, c.d_ehi, nullptr, d_grad);
+  else
+    grad_reduce_kernel<false><<<batch * c.S, 256, 0, st>>>(c.S, c.E, cap, d_pos, d_w01, d_ow, nullptr, 0, nullptr,
+                                                           nullptr, (const double*)c.d_eT, d_grad);
+  return hipGetLastError();
+}
+
+}  // namespace nemo

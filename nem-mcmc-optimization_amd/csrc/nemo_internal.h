@@ -112,6 +112,15 @@ struct Ctx {
   double* d_wuw = nullptr;         // [S][2] U - U[S] of row i at D1 bit 0 / 1
   double* d_wnull = nullptr;       // [nwords] sum of U[S][e] over each 64-effect word
 
+  // order-score gradient in the weights (nemo_grad.hip): option "grad_path"
+  // 0 auto (the fused kernel for a factored model with S <= 64, else the
+  // two-pass path), 1 = always two-pass; grad_path_used: what the last call ran
+  int grad_path = 0;
+  int grad_path_used = 0;
+  double* d_grad = nullptr;        // [cap][S][S] the host entry's gradient
+  double* d_gradM = nullptr;       // [cap][grad_parts][grad_part_doubles] the fused kernel's partial M tiles
+  double* d_gradll = nullptr;      // [cap][grad_parts] its partial ll
+
   // the reference's own arithmetic in the fused step and the sampler's ll-only
   // calls (nemo_exact.hip): option "exact" (1 default), available when the
   // staged model is factored and numpy's pairwise sum of E fits the wave plan
@@ -413,6 +422,51 @@ __device__ __forceinline__ double log_fast(double x, const double2* __restrict__
   return fma(kd, kLn2Hi, tj.y) + fma(kd, kLn2Lo, p);
 }
 
+// exp(x) for x <= ~0 in fp64 from a 64-entry table of 2^(j/64) and a
+// degree-5 polynomial on |r| <= ln2/128 (truncation < 4e-17): ~12 VALU ops
+// instead of the ~25 of the general exp; relative error a few ulp.
+__device__ __forceinline__ double exp_tab(double x, const double* __restrict__ tab) {
+  constexpr double kInvLn2x64 = 92.332482616893656768;     // 64 / ln 2
+  constexpr double kLn2d64Hi = 1.0830424696223417e-02;     // ln2/64, high part
+  constexpr double kLn2d64Lo = 2.5728046223276690e-14;     // ln2/64 - high part
+  x = fmax(x, -1000.0);
+  const double kf = rint(x * kInvLn2x64);
+  const int k = (int)kf;
+  double r = fma(-kf, kLn2d64Hi, x);
+  r = fma(-kf, kLn2d64Lo, r);
+  double p = fma(r, 1.0 / 120.0, 1.0 / 24.0);
+  p = fma(r, p, 1.0 / 6.0);
+  p = fma(r, p, 0.5);
+  p = fma(r, p, 1.0);
+  p = fma(r, p, 1.0);
+  return ldexp(p * tab[k & 63], k >> 6);
+}
+
+// exp(x) for finite x in [-1e12, ~0] (the log-sum-exp terms): 256-entry
+// table of 2^(j/256) and a degree-4 polynomial on |r| <= ln2/512 (truncation
+// < 4e-17).  k = round(x * 256/ln2) comes from the low word of
+// fma(x, 256/ln2, 1.5*2^52) (no clamp, rint or cvt), and the reduction uses
+// one constant: its error, |x| * 1.6e-16 relative, is weighted by e^x in the
+// sum (< 1e-16 of it).  9 f64 VALU + 3 integer.
+__device__ __forceinline__ double exp_lse(double x, const double* __restrict__ tab) {
+  constexpr double kInvLn2x256 = 369.32993046757462707;  // 256 / ln 2
+  constexpr double kLn2d256 = 2.7076061740622862e-03;    // ln 2 / 256
+  constexpr double kMagic = 6755399441055744.0;          // 1.5 * 2^52
+  const double t = fma(x, kInvLn2x256, kMagic);
+  const double kf = t - kMagic;
+  const int k = (int)(uint32_t)__builtin_bit_cast(uint64_t, t);
+  const double r = fma(-kf, kLn2d256, x);
+  double p = fma(r, 1.0 / 24.0, 1.0 / 6.0);
+  p = fma(r, p, 0.5);
+  p = fma(r, p, 1.0);
+  p = fma(r, p, 1.0);
+  return ldexp(p * tab[k & 255], k >> 8);
+}
+
+// value of the G column on padding rows (q >= S): cells of padding rows are
+// U[S][e] + kPadG, whose exp underflows to exactly 0 next to any real row
+constexpr double kPadG = -1.0e6;
+
 // Cross-lane sums of a double without the LDS (DPP moves and permlane swaps are
 // VALU; __shfl_xor goes through ds_bpermute).
 // DPP move of a double (both dwords), dpp_ctrl CTRL over all rows / banks
@@ -568,6 +622,10 @@ hipError_t launch_ancestral(Ctx& c, int nprob, const int32_t* d_pos, const doubl
 // then the commit of the level's optima into d_w
 hipError_t launch_inverse_level(Ctx& c, int n, const int32_t* d_list, const int32_t* d_pos, double* d_w,
                                 const double* d_ow, double* d_xout, int32_t* d_info, hipStream_t st);
+// prep_factored_kernel alone: Delta (+ the G column), G and perm of the batch
+// into d_fDp / d_fG / d_fperm (cap already effective: 0 when it cuts nothing)
+hipError_t launch_prep_factored(Ctx& c, int batch, int cap, const int32_t* d_pos, const double* d_w01,
+                                hipStream_t st);
 // prepped: Delta / G / perm of the batch are already staged (step_prep_kernel);
 // defer_np: when set, the per-evaluation partials are left unsummed and
 // *defer_np = their count (0 if the kernel summed them itself)
@@ -575,6 +633,30 @@ hipError_t launch_score_factored(Ctx& c, int batch, int cap, const int32_t* d_po
                                  const double* d_w01, double* d_ll, double* d_cs, double* d_cells,
                                  double* d_ow, hipStream_t st, bool prepped = false,
                                  int* defer_np = nullptr);
+// ---- order-score gradient d ll / d w01 (nemo_grad.hip) ----
+// The fused kernel cuts E into parts of kGradWaves * kGradTilesPerWave
+// 16-effect tiles, one block each: a function of the staged E alone, so an
+// evaluation's bits do not depend on the batch.  A part leaves the
+// accumulator tiles of M^T with p-block <= q-block in C-fragment order.
+constexpr int kGradWaves = 8, kGradTilesPerWave = 8;
+inline int grad_parts(int E) {
+  const int tpb = kGradWaves * kGradTilesPerWave;
+  return ((E + 15) / 16 + tpb - 1) / tpb;
+}
+inline size_t grad_part_doubles(int spad) {
+  const size_t nr = (size_t)spad / 16;
+  return nr * (nr + 1) / 2 * 256;
+}
+inline bool grad_fused_shape(const Ctx& c) { return c.dtype == 0 && factored_spad(c.S) <= 64; }
+// fused: prep_factored_kernel, the fused kernel and its finish (factored model,
+// S <= 64); ll [batch], grad [batch][S][S] (every entry written)
+hipError_t launch_score_grad_fused(Ctx& c, int batch, int cap, const int32_t* d_pos, const double* d_w01,
+                                   double* d_ll, double* d_grad, hipStream_t st);
+// the two-pass path's second pass: the reduction over (evaluation, child,
+// parent) of the order weights d_ow [batch][S+1][E] against the D1 bits
+// (factored) or the staged exp(T) rows (generic, fp64)
+hipError_t launch_grad_reduce(Ctx& c, int batch, int cap, bool factored, const int32_t* d_pos,
+                              const double* d_w01, const double* d_ow, double* d_grad, hipStream_t st);
 // the fused step's prep in ONE launch: prep_kernel's parent and pair lists
 // with the info rows preset to -1, and prep_factored_kernel's Delta / G / perm
 hipError_t launch_step_prep(Ctx& c, int batch, int cap, const int32_t* d_pos, const double* d_w01,

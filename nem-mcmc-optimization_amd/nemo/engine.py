@@ -191,6 +191,25 @@ class Engine:
             check(lib.nemo_score_group_dev(self._ctx, int(batch), int(group), d_pos, d_w01,
                                            int(cap), d_ll, stream))
 
+    # -- d ll / d w01 ---------------------------------------------------------
+    def score_grad(self, pos, w01, cap: int = 0):
+        """Order scores and their gradient in the mapped weights: (ll (B,),
+        grad (B, S, S)), grad[b, i, j] = d ll[b] / d w01[b, i, j] at the
+        permissible pairs and exactly 0 elsewhere (fp64 engines only)."""
+        pos = i32(np.atleast_2d(pos))
+        b = pos.shape[0]
+        w01 = f64(w01).reshape(b, self.S, self.S)
+        ll = np.empty(b)
+        grad = np.empty((b, self.S, self.S))
+        a = _lib.addr
+        check(_lib.load().nemo_score_grad(self._ctx, b, a(pos), a(w01), int(cap), a(ll), a(grad)))
+        return ll, grad
+
+    def score_grad_dev(self, batch, d_pos, d_w01, d_ll, d_grad, cap=0, stream=None):
+        """Enqueue ``score_grad`` on device pointers (no sync; ``reserve``
+        the batch first)."""
+        check(_lib.load().nemo_score_grad_dev(self._ctx, int(batch), d_pos, d_w01, int(cap), d_ll, d_grad, stream))
+
     # -- utils.compute_ll / calculate_ll on a given cell matrix ------------
     def lse(self, cells, want_ow=False):
         cells = f64(cells)

@@ -169,4 +169,54 @@ class Method(_Base):
         return weights.T, real_ll
 
 
-__all__ = ["InverseMethod", "Method", "INVERSE_BOUNDS", "GAMMA_BOUNDS"]
+class JointMethod(_Base):
+    """All weights of a fixed order at once: logits X on the permissible
+    pairs, w = expit(X), L-BFGS with a strong-Wolfe line search on -ll through
+    ``nemo.autograd.order_score`` (the engine's gradient kernels).
+
+    This is the working form of what the reference's
+    ``NEMOrderMCMC.opt_weights`` / ``global_opt_fun`` (nem_order_mcmc.py:
+    105-150) meant and crashes on; there is no reference output to match, so
+    no parity is claimed.  The constructor, ``ll_list`` / ``best_ll`` and
+    ``optimize``'s return follow ``Method``."""
+
+    def optimize(self, max_iter=50, rel_diff=1e-8, use_wandb=False):
+        """-> (rounded weights.T, rounded ll).  One entry of ``ll_list`` per
+        evaluation of the closure (the first: every weight 0.5, ``Method``'s
+        start); the weights of the best one are kept (``best_weights``,
+        ``best_ll``), like the reference's ``best_index`` bookkeeping."""
+        import torch
+
+        from .autograd import order_score
+        eng = self.engine
+        dev = torch.device("cuda", eng.device)
+        pos = torch.from_numpy(self._pos[None, :].copy()).to(dev)
+        mask = torch.from_numpy(self.mask[None] > 0).to(dev)
+        x = torch.zeros((1, self.num_s, self.num_s), dtype=torch.float64, device=dev, requires_grad=True)
+        opt = torch.optim.LBFGS([x], max_iter=int(max_iter), tolerance_change=float(rel_diff),
+                                line_search_fn="strong_wolfe")
+        ll_list, best = [], {"ll": -float("inf"), "w": None}
+
+        def closure():
+            opt.zero_grad()
+            w = torch.where(mask, torch.sigmoid(x), torch.zeros_like(x))
+            ll = order_score(eng, pos, w)[0]
+            (-ll).backward()
+            v = float(ll.detach())
+            ll_list.append(v)
+            if v > best["ll"]:
+                best["ll"], best["w"] = v, w.detach()[0].cpu().numpy()
+            return -ll
+
+        opt.step(closure)
+        self.ll_list = ll_list
+        self.best_ll = best["ll"]
+        self.best_weights = best["w"]
+        print(f"Best ll: {self.best_ll}")
+        weights = 1 * (self.best_weights > 0.5)
+        real_ll = self._ll_of(weights)
+        print(f"Rounded LL: {real_ll}")
+        return weights.T, real_ll
+
+
+__all__ = ["InverseMethod", "Method", "JointMethod", "INVERSE_BOUNDS", "GAMMA_BOUNDS"]
