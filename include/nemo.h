@@ -257,6 +257,25 @@ int nemo_inverse_ancestral(nemo_ctx* ctx, int nprob, const int32_t* pos, const d
 int nemo_inverse_sweep(nemo_ctx* ctx, int nprob, const int32_t* pos, const double* w, double* w_out,
                        double* ll_out, int32_t* info);
 
+/* ---- NEM.compute_real_score's sweep (nem.py:112-125) ------------------------
+ * One pass of the reference's fit of the true graph, for nprob problems (one
+ * order each): the evaluation on the weights w (ll_out, order weights kept on
+ * the device), then for every permissible pair (i, j)
+ *   minimize(-sum log(c x + 1), x0 = 0.5, bounds [(0, 1)], L-BFGS-B, tol 0.1)
+ * with c = a / b, a = (exp(T[i][j]) - 1) * order_weights -- the whole
+ * (S+1, E) matrix, T's row broadcast over its rows (nem.py:117) -- and
+ * b = 1 - w[i][j] a + w[i][j] (exp(T[i][j]) - 1); no jac (forward differences,
+ * step 1e-8, flipped at the bound), x0 always 0.5.  w, w_out, ll_out, info as
+ * for nemo_gamma_sweep (no cap).  A solve that ends abnormally is no error
+ * (the reference keeps res.x without reading res.success): the call returns
+ * NEMO_OK and the status is in info.  One block per pair streams the order
+ * weights, so E is bounded only by what the context stages; every sum has a
+ * fixed order: a pair's bits depend neither on nprob nor on its slot.
+ * NEMO_F64 contexts, factored or generic (NEMO_F32: NEMO_ERR_ARG); a wide
+ * table (|T| > 170, option "exact_generic") is refused like the other sweeps. */
+int nemo_real_sweep(nemo_ctx* ctx, int nprob, const int32_t* pos, const double* w, double* w_out,
+                    double* ll_out, int32_t* info);
+
 /* ---- options -------------------------------------------------------------
  *   "xcd_remap"  1 (default) XCD-aware block order; speed only
  *   "score_path" 0 (default) auto: the factored MFMA kernel when the staged
@@ -398,7 +417,8 @@ int nemo_inverse_sweep(nemo_ctx* ctx, int nprob, const int32_t* pos, const doubl
  *                cached throughput, 5 dual, 6 the throughput form over several
  *                plan parts, 7 slot); 0 before any launch
  *   "timing_kernel" 0 (default): nemo_timing_enable / _read time the score
- *                kernels; 1: the exact local optima's kernel (bench.py)
+ *                kernels; 1: the exact local optima's kernel (bench.py);
+ *                2: nemo_real_sweep's pair solves (tools/real_score_time.py)
  *   "anc_overlap" 1 (default): nemo_optimal_weights_w makes ancestor_x on a
  *                second stream beside eval #1 (same bits); 0 = in line */
 int nemo_set_option(nemo_ctx* ctx, const char* name, int value);

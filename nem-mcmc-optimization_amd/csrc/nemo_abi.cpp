@@ -1664,6 +1664,40 @@ int nemo_inverse_sweep(nemo_ctx* ctx, int nprob, const int32_t* pos, const doubl
   return opt_status(c, inf, nprob);
 }
 
+int nemo_real_sweep(nemo_ctx* ctx, int nprob, const int32_t* pos, const double* w, double* w_out, double* ll_out,
+                    int32_t* info) {
+  int rc = check_ctx(ctx, true);
+  if (rc) return rc;
+  Ctx& c = ctx->c;
+  if (c.dtype != NEMO_F64)
+    return fail(NEMO_ERR_ARG, "nemo_real_sweep: dtype f32 (NEMO_F32) context; the pair solves are fp64 only (NEMO_F64)");
+  if (nprob < 0) return fail(NEMO_ERR_ARG, "nprob=%d", nprob);
+  if (nprob == 0) return NEMO_OK;
+  if (!pos || !w || !w_out || !ll_out) return fail(NEMO_ERR_ARG, "null host pointer");
+  if (nprob > 32767) return fail(NEMO_ERR_ARG, "nprob=%d > 32767", nprob);
+  if ((rc = refuse_wide(c, "nemo_real_sweep"))) return rc;
+  if ((rc = check_pos(pos, nprob, c.S))) return rc;
+  if ((rc = nemo_reserve(ctx, nprob, nprob))) return rc;
+  const size_t S = c.S;
+  hipStream_t st = c.stream;
+  HIPCHK(hipMemcpyAsync(c.d_pos, pos, nprob * S * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(c.d_w01, w, nprob * S * S * 8, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(c.d_wnew, c.d_w01, nprob * S * S * 8, hipMemcpyDeviceToDevice, st));
+  HIPCHK(hipMemsetAsync(c.d_info, 0xff, nprob * S * S * 4, st));
+  // the sweep's evaluation (nem.py:113), order weights left in d_ow; then
+  // every pair's solve against the whole of them (:114-121)
+  if ((rc = eval_with_ow(c, nprob, 0, c.d_w01, st))) return rc;
+  c.ow_chains = 0;  // (the fused step's accessor reads its own evaluations only)
+  HIPCHK(nemo::launch_real_pairs(c, nprob, nemo::pairs_per_chain(c.S, 0), use_factored(c), c.d_pairs, c.d_w01,
+                                 c.d_ow, c.d_wnew, c.d_info, st));
+  HIPCHK(hipMemcpyAsync(w_out, c.d_wnew, nprob * S * S * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(ll_out, c.d_ll, nprob * 8, hipMemcpyDeviceToHost, st));
+  if (info) HIPCHK(hipMemcpyAsync(info, c.d_info, nprob * S * S * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  // no NEMO_ERR_OPT: the reference keeps res.x whatever res.success says
+  return NEMO_OK;
+}
+
 int nemo_set_option(nemo_ctx* ctx, const char* name, int value) {
   int rc = check_ctx(ctx, false);
   if (rc) return rc;
@@ -1708,7 +1742,8 @@ int nemo_set_option(nemo_ctx* ctx, const char* name, int value) {
     return NEMO_OK;
   }
   if (strcmp(name, "timing_kernel") == 0) {
-    if (value < 0 || value > 1) return fail(NEMO_ERR_ARG, "timing_kernel %d (0 score kernels, 1 exact local optima)", value);
+    if (value < 0 || value > 2)
+      return fail(NEMO_ERR_ARG, "timing_kernel %d (0 score kernels, 1 exact local optima, 2 real-score pair solves)", value);
     ctx->c.timing_kernel = value;
     return NEMO_OK;
   }

@@ -245,7 +245,8 @@ struct Ctx {
   int step_graph_next = 0;
 
   // timing of the score kernel (timing_kernel 0) or of the exact local
-  // optima's kernel (1; option "timing_kernel")
+  // optima's kernel (1) or of the real-score pair solves (2; option
+  // "timing_kernel")
   bool timing = false;
   int timing_kernel = 0;
   std::vector<hipEvent_t> ev_pool;
@@ -616,6 +617,13 @@ __device__ __forceinline__ double sum_partials(const double* __restrict__ p, int
 hipError_t launch_gamma_pairs(Ctx& c, int nprob, int npairs, const int32_t* d_pairs, const int32_t* d_rows,
                               const double* d_w, const double* d_ow, double* d_wout, int32_t* d_info,
                               hipStream_t st);
+// NEM.compute_real_score's pair solves (nemo_realscore.hip): one block per
+// (problem, permissible pair) streams the problem's order weights d_ow
+// [nprob][S+1][E]; factored: v from the D1 bits, else the staged exp(T) rows
+// (fp64 contexts only)
+hipError_t launch_real_pairs(Ctx& c, int nprob, int npairs, bool factored, const int32_t* d_pairs,
+                             const double* d_w, const double* d_ow, double* d_wout, int32_t* d_info,
+                             hipStream_t st);
 hipError_t launch_ancestral(Ctx& c, int nprob, const int32_t* d_pos, const double* d_w, double* d_out,
                             hipStream_t st);
 // one level of InverseMethod.opt_b's pair loop (list entries prob << 16 | i << 8 | k),

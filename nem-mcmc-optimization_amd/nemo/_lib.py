@@ -68,6 +68,7 @@ SIGNATURES = [
     ("nemo_gamma_sweep", C.c_int, [_vp, C.c_int, _i32p, _f64p, C.c_int, _f64p, _f64p, _i32p]),
     ("nemo_inverse_ancestral", C.c_int, [_vp, C.c_int, _i32p, _f64p, _f64p]),
     ("nemo_inverse_sweep", C.c_int, [_vp, C.c_int, _i32p, _f64p, _f64p, _f64p, _i32p]),
+    ("nemo_real_sweep", C.c_int, [_vp, C.c_int, _i32p, _f64p, _f64p, _f64p, _i32p]),
     ("nemo_set_option", C.c_int, [_vp, C.c_char_p, C.c_int]),
     ("nemo_get_option", C.c_int, [_vp, C.c_char_p, _i32p]),
     ("nemo_set_option_f64", C.c_int, [_vp, C.c_char_p, C.c_double]),

@@ -305,6 +305,14 @@ class Engine:
         """``InverseMethod.opt_b`` (methods.py:117-129) per problem: (w_out, ll, info)."""
         return self._sweep(_lib.load().nemo_inverse_sweep, pos, w, raise_on_fail=raise_on_fail)
 
+    def real_sweep(self, pos, w):
+        """One sweep of ``NEM.compute_real_score``'s fit (nem.py:112-125) per
+        problem: the evaluation on ``w``, then every permissible pair's
+        bounded solve from 0.5 against the whole order-weight matrix:
+        (w_out, ll, info).  A solve's status is in ``info`` only (the
+        reference keeps ``res.x`` unchecked).  fp64 engines only."""
+        return self._sweep(_lib.load().nemo_real_sweep, pos, w)
+
     def inverse_ancestral(self, pos, w):
         """unorder_arr(order, B/(1+B)), B = (I - order_arr(order, exp(w)))^-1 lower
         (methods.py:118-121, :160-164), per problem."""

@@ -67,10 +67,14 @@ def output_handling(best_dag, network_path=None, out_dir="output") -> dict:
 
 
 def run_network(csv_path, method="inverse", n_iterations=500, swap_prob=0.90, n_exchange=20,
-                replica_iters=300, out_dir=None, device=0, engine=None, verbose=False) -> dict:
+                replica_iters=300, out_dir=None, device=0, engine=None, verbose=False,
+                real_score=False) -> dict:
     """main.py:56-121 for one network CSV.  Returns the best DAG, its score,
     the Hamming distances main() prints and (with ``out_dir``) the DOT
-    paths.  The random stream is the global ``random`` one, left where the
+    paths.  ``real_score``: also fit the true graph (``NEM.real_scores``, the
+    two ``compute_real_score`` calls of the reference's constructor) and
+    return ``observed_score`` / ``observed_order_score`` (``obs_ll`` /
+    ``obs_order_ll``, the yardstick main.py:126 prints).  The random stream is the global ``random`` one, left where the
     NEM constructor puts it (reseeded 42, then S*E draws), as in main()."""
     from .engine import Engine
     adj_matrix, end_nodes, errors, num_s, num_e = utils.read_csv_to_adj(csv_path)
@@ -106,6 +110,11 @@ def run_network(csv_path, method="inverse", n_iterations=500, swap_prob=0.90, n_
     if verbose:
         print(f"Hamming Distance: {result['hamming']}")
         print(f"Hamming Distance to Ancestor: {result['hamming_ancestor']}")
+    if real_score:
+        my_nem.real_scores(device=device)
+        result.update(observed_score=my_nem.obs_ll, observed_order_score=my_nem.obs_order_ll)
+        if verbose:
+            print(f"Observed Score: {my_nem.obs_ll}")
     if out_dir is not None:
         base = os.path.splitext(csv_path)[0]
         result["paths"] = output_handling(best_dag, base, out_dir)
@@ -119,9 +128,11 @@ def main(argv=None) -> None:
     ap.add_argument("--iterations", type=int, default=500)
     ap.add_argument("--out", default="output")
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--real-score", action="store_true",
+                    help="also fit the true graph and print its observed score (main.py:126)")
     a = ap.parse_args(argv)
     r = run_network(a.network, a.method, n_iterations=a.iterations, out_dir=a.out, device=a.device,
-                    verbose=True)
+                    verbose=True, real_score=a.real_score)
     print(f"Score: {r['score']}")
 
 

@@ -15,6 +15,12 @@ same addition chain through a lookup table instead of an S*S*E Python loop.
 
 The tables are staged to HBM once by :class:`nemo.engine.Engine`; nothing in
 this file is on the per-step path.
+
+The true graph's scores (``compute_real_score``, nem.py:88-144; the six
+``real_*`` / ``obs_*`` attributes the reference's constructor fills) are made
+by :meth:`NEM.real_scores` on request: the host keeps the fit's loop, each of
+its sweeps -- every permissible pair's bounded L-BFGS-B solve -- is one GPU
+call (``Engine.real_sweep``), and construction itself stays free of GPU work.
 """
 from __future__ import annotations
 
@@ -151,11 +157,14 @@ class NEM:
     started afterwards sees the same proposal stream.
 
     The reference also runs ``compute_real_score`` twice at construction
-    (nem.py:21-22), a diagnostic L-BFGS-B fit of the *true* graph that does not
-    feed the sampler.  It is out of scope here; its only
-    side effect on shared state -- zeroing the caller's adjacency diagonal in
-    place (nem.py:90-91) -- is reproduced, and the diagnostic attributes are
-    left as ``None``.
+    (nem.py:21-22), an L-BFGS-B fit of the *true* graph that does not feed the
+    sampler: the yardstick its users read a run against (``obs_ll``).  Here
+    construction does no GPU work: its only side effect on shared state --
+    zeroing the caller's adjacency diagonal in place (nem.py:90-91) -- is
+    reproduced, and the six attributes ``real_order_ll``, ``real_ll``,
+    ``real_parent_order``, ``obs_order_ll``, ``obs_ll``, ``obs_parent_order``
+    stay ``None`` until :meth:`real_scores` runs the two fits on the GPU
+    (``nemo_real_sweep``: every pair's solve of a sweep in one call).
     """
 
     def __init__(self, adj_matrix, end_nodes, errors, num_s, num_e, seed=42):
@@ -246,3 +255,75 @@ class NEM:
         chain0, _ = self._chains()
         null_row = chain0[(self.observed_knockdown_mat != 0).sum(axis=0)]
         return np.vstack(rows + [null_row])
+
+    # -- the true graph's scores (nem.py:88-144) ------------------------------
+    def compute_real_score(self, real_knockdown_mat, adj_mat, device: int = 0):
+        """Reference: nem.py:88-144, on the GPU.  Returns ``(real_order_ll,
+        real_ll, parent_order)`` for the tables of ``real_knockdown_mat``:
+
+        * ``parent_order``: the S-genes by descending row sum of ``adj_mat``
+          (diagonal zeroed in place; numpy's argsort, so ties fall as there);
+        * the order's parent weights are fitted from 0.5 by sweeps
+          (``Engine.real_sweep``: the evaluation, then every permissible
+          pair's bounded solve against the whole order-weight matrix) while
+          the evaluation's ll rose by more than 1e-4 (signed, at most 1000
+          sweeps); the last sweep's weights are kept;
+        * ``real_order_ll``: the order score at ``1 * (w > 0.5)``;
+        * ``real_ll``: the score with the adjacency's own parent sets at
+          weight 1 (i is a parent of j where ``adj_mat[i][j] == 1``).
+
+        The node table's null row comes from ``observed_knockdown_mat``
+        whatever ``real_knockdown_mat`` is (nem.py:62).  The host keeps only
+        the loop; ``real_score_trace`` holds the last call's per-sweep ll and
+        weights.  An edge of ``adj_mat`` that points backwards in
+        ``parent_order`` (an adjacency not in closure form) raises
+        ``ValueError``: the engine scores permissible parents only."""
+        from .engine import Engine
+        s = self.num_s
+        for i in range(s):
+            adj_mat[i][i] = 0
+        row_sums = np.sum(adj_mat, axis=1)
+        parent_order = np.argsort(row_sums)[::-1]
+        pos = np.empty(s, dtype=np.int32)
+        pos[parent_order] = np.arange(s, dtype=np.int32)
+        adj = np.asarray(adj_mat)
+        for i, j in zip(*np.nonzero(adj == 1)):
+            if pos[i] >= pos[j]:
+                raise ValueError(f"edge {i}->{j} of adj_mat points backwards in parent_order "
+                                 f"(positions {pos[i]} and {pos[j]}): the adjacency is not in closure form")
+        tables = self.get_score_tables(real_knockdown_mat)
+        chain0, _ = self._chains()
+        null_row = chain0[(np.asarray(self.observed_knockdown_mat) != 0).sum(axis=0)]
+        u_mixed = np.vstack([self.compute_scores(i, real_knockdown_mat) for i in range(s)] + [null_row])
+        eng = Engine.for_tables(u_mixed, tables, device=device)
+        mask = pos[None, :] < pos[:, None]          # mask[i, j]: j is a permissible parent of i
+        w = np.where(mask, 0.5, 0.0)
+        ll_diff, old_ll, iter_count = float("inf"), -float("inf"), 0
+        ll_list, w_list = [], []
+        while ll_diff > 0.0001 and iter_count < 1000:
+            w_out, ll, _info = eng.real_sweep(pos, w)
+            w = np.where(mask, w_out[0], 0.0)
+            ll_diff = float(ll[0]) - old_ll
+            old_ll = float(ll[0])
+            iter_count += 1
+            ll_list.append(old_ll)
+            w_list.append(w)
+        rounded = np.where(mask, 1.0 * (w > 0.5), 0.0)
+        real_order_ll = float(eng.score(pos, rounded)[0])
+        real_ll = float(eng.score(pos, (adj == 1).T.astype(np.float64))[0])
+        self.real_score_trace = {"sweeps": iter_count, "ll": np.array(ll_list), "weights": np.array(w_list),
+                                 "rounded": rounded, "pos": pos}
+        return real_order_ll, real_ll, parent_order
+
+    def real_scores(self, device: int = 0):
+        """The two calls of the reference's constructor (nem.py:21-22): the
+        fit on the real and on the observed knockdown matrix; fills
+        ``real_order_ll``, ``real_ll``, ``real_parent_order`` and ``obs_*``
+        and returns ``self``."""
+        self.real_order_ll, self.real_ll, self.real_parent_order = self.compute_real_score(
+            self.real_knockdown_mat, self.adj_matrix, device=device)
+        self.real_trace = self.real_score_trace
+        self.obs_order_ll, self.obs_ll, self.obs_parent_order = self.compute_real_score(
+            self.observed_knockdown_mat, self.adj_matrix, device=device)
+        self.obs_trace = self.real_score_trace
+        return self
