@@ -142,6 +142,52 @@ int nemo_score_grad(nemo_ctx* ctx, int batch, const int32_t* pos, const double* 
 int nemo_score_grad_dev(nemo_ctx* ctx, int batch, const int32_t* d_pos, const double* d_w01, int cap,
                         double* d_ll, double* d_grad, void* stream);
 
+/* ---- the error rates as parameters: score and gradient in per-gene A_k, B_k --
+ * The closing comment of nem.py ("shared probability between clusters for the
+ * error rates, use that as a latent variable") names what the reference never
+ * built; no reference counterpart runs, so "exact" / "exact_dev" /
+ * "fact_kernel" do not route this call.  Every evaluation carries its own
+ * rates, per S-gene: A_k = log(alpha_k / (1 - beta_k)), B_k = log(beta_k /
+ * (1 - alpha_k)), and nothing is restaged.  With D the staged knockdown
+ * matrix the tables of nem.py:25-64 generalise to
+ *   T[i][j][e] = D[j][e] ? -A_j : B_j                      (j != i),
+ *   U[i][e]    = (D[i][e] ? 0 : B_i) + sum_{k != i} D[k][e] A_k,
+ *   U[S][e]    = sum_k D[k][e] A_k
+ * (scalar rates: the staged tables up to the rounding of their addition
+ * chains), and the call evaluates the offset form, n_k = sum_e D[k][e]:
+ *   x[i][e] = (D[i][e] ? -A_i : B_i) + sum_{j in pa(i)} log(1 - w + w e^{T[i][j][e]})
+ *   ll      = sum_k A_k n_k + sum_e log(1 + sum_i exp(x[i][e])).
+ *   rates      [batch][2][S]   row 0: A_k, row 1: B_k of each evaluation
+ *   ll_out     [batch]         as nemo_score at those rates
+ *   drates_out [batch][2][S]   row 0: d ll / d A_k, row 1: d ll / d B_k; with
+ *                              ow = exp(cell - cs), w = w01[i][k] over the
+ *                              children i that have k as a permissible parent,
+ *       d ll / d A_k = sum_e D[k][e] (1 - ow[k][e] - sum_i h_ik ow[i][e]),
+ *       d ll / d B_k = sum_e (1 - D[k][e]) (ow[k][e] + sum_i k_ik ow[i][e]),
+ *       h_ik = w e^{-A_k} / (1 - w + w e^{-A_k}),  k_ik = w e^{B_k} / (1 - w + w e^{B_k})
+ *   grad_out   [batch][S][S]   d ll / d w01 as nemo_score_grad at these rates
+ *                              (nullable; exactly 0.0 off the permissible pairs,
+ *                              where w01 is not read)
+ * ll is a ratio against a baseline that depends on the rates; a fit maximises
+ *   L = ll + sum_k [ n_k log(1 - beta_k) + (E - n_k) log(1 - alpha_k) ]
+ * (nemo.rates.absolute_ll).  One fused MFMA launch between a prep and a finish;
+ * every sum has a fixed order that depends on E and the evaluation alone: an
+ * evaluation's bits depend neither on the batch nor on its slot nor on the run.
+ * Serves NEMO_F64 contexts (NEMO_F32: NEMO_ERR_ARG) with S <= 64 (more:
+ * NEMO_ERR_ARG -- past 64 the forward runs in two passes and reads the staged
+ * U) staged by nemo_stage_knockdown (else NEMO_ERR_STATE: generic and
+ * log-ratio tables have no rates), with any cap.  The host entry wants every
+ * rate finite with |A_k|, |B_k| <= 700, so that e^{-A} stays finite (else
+ * NEMO_ERR_ARG).  _dev: enqueue only; after nemo_reserve(max_batch, .) with
+ * batch <= max_batch it neither allocates nor synchronises (else
+ * NEMO_ERR_STATE); it cannot validate the rates: non-finite rates give
+ * non-finite outputs and nothing worse. */
+int nemo_score_rates(nemo_ctx* ctx, int batch, const int32_t* pos, const double* w01, const double* rates,
+                     int cap, double* ll_out, double* drates_out, double* grad_out);
+int nemo_score_rates_dev(nemo_ctx* ctx, int batch, const int32_t* d_pos, const double* d_w01,
+                         const double* d_rates, int cap, double* d_ll, double* d_drates, double* d_grad,
+                         void* stream);
+
 /* reuse-batched variant: `group` evaluations share every table row read
  * (group in {1,4,8,16}); same results as nemo_score_dev */
 int nemo_score_group_dev(nemo_ctx* ctx, int batch, int group, const int32_t* d_pos, const double* d_w01,

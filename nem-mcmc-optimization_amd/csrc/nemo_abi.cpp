@@ -188,7 +188,8 @@ void nemo_ctx_destroy(nemo_ctx* ctx) {
                   c.d_xlo,  c.d_xhi,  c.d_pwplan, c.d_xcs, c.d_xcells2, c.d_xcbuf,
                   c.d_xa,   c.d_xbits, c.d_pwpos, c.d_pwmeta, c.d_xtrace, c.d_xqueue,
                   c.d_xcost, c.d_xorder, c.d_xhist, c.d_xsbuf, c.d_xX, c.d_xl,
-                  c.d_grad, c.d_gradM, c.d_gradll};
+                  c.d_grad, c.d_gradM, c.d_gradll, c.d_Dw, c.d_nk, c.d_rexp, c.d_rdiag,
+                  c.d_rates, c.d_drates};
   for (void* p : bufs)
     if (p) (void)hipFree(p);
   for (int k = 0; k < Ctx::kStepSlots; ++k) {
@@ -239,6 +240,12 @@ int nemo_reserve(nemo_ctx* ctx, int max_batch, int max_chains) {
         const size_t np = (size_t)nemo::grad_parts(c.E);
         HIPCHK(dalloc(&c.d_gradM, nb * np * nemo::grad_part_doubles((int)sp)));
         HIPCHK(dalloc(&c.d_gradll, nb * np));
+        // nemo_score_rates: each evaluation's exponentials, the partial M_kk
+        // and the host entry's rates and derivatives
+        HIPCHK(dalloc(&c.d_rexp, nb * 2 * S));
+        HIPCHK(dalloc(&c.d_rdiag, nb * np * sp));
+        HIPCHK(dalloc(&c.d_rates, nb * 2 * S));
+        HIPCHK(dalloc(&c.d_drates, nb * 2 * S));
       }
     }
     c.cap_batch = nb;
@@ -296,6 +303,7 @@ int alloc_tables(Ctx& c) {
   const size_t esz = c.dtype == NEMO_F64 ? 8 : 4;
   HIPCHK(hipStreamSynchronize(c.stream));
   c.staged = false;
+  c.knockdown = false;  // (set again by nemo_stage_knockdown)
   c.xg_ok = false;   // (set again by the staging of a covered generic table, option exact_generic)
   void** bufs[] = {&c.d_eT, &c.d_U, (void**)&c.d_U64};
   for (void** p : bufs)
@@ -646,7 +654,25 @@ int nemo_stage_knockdown(nemo_ctx* ctx, const uint8_t* D, double A, double B) {
   std::vector<uint64_t> d1;
   std::vector<double> elo, ehi, tlo, thi;
   nemo::host::knockdown_factored(c.S, c.E, D, A, B, d1, elo, ehi, &tlo, &thi);
-  return stage_factored(ctx, ufin, d1, elo, ehi, tlo, thi);
+  if ((rc = stage_factored(ctx, ufin, d1, elo, ehi, tlo, thi))) return rc;
+  // nemo_score_rates (fp64, S <= 64): D's own bits and the row counts n_k
+  if (nemo::grad_fused_shape(c)) {
+    const size_t nw = (E + 63) / 64;
+    std::vector<uint64_t> dw(S * nw, 0ull);
+    std::vector<double> nk(S, 0.0);
+    for (size_t k = 0; k < S; ++k)
+      for (size_t e = 0; e < E; ++e)
+        if (D[k * E + e]) {
+          dw[k * nw + e / 64] |= 1ull << (e % 64);
+          nk[k] += 1.0;
+        }
+    HIPCHK(dalloc(&c.d_Dw, dw.size()));
+    HIPCHK(dalloc(&c.d_nk, S));
+    HIPCHK(nemo::copy_sync(c, c.d_Dw, dw.data(), dw.size() * 8, hipMemcpyHostToDevice));
+    HIPCHK(nemo::copy_sync(c, c.d_nk, nk.data(), S * 8, hipMemcpyHostToDevice));
+    c.knockdown = true;
+  }
+  return NEMO_OK;
 }
 
 static bool use_factored(const Ctx& c) {
@@ -873,6 +899,63 @@ int nemo_score_grad(nemo_ctx* ctx, int batch, const int32_t* pos, const double* 
   if ((rc = nemo_score_grad_dev(ctx, batch, c.d_pos, c.d_w01, cap, c.d_ll, c.d_grad, st))) return rc;
   HIPCHK(hipMemcpyAsync(ll_out, c.d_ll, batch * 8, hipMemcpyDeviceToHost, st));
   HIPCHK(hipMemcpyAsync(grad_out, c.d_grad, batch * S * S * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return NEMO_OK;
+}
+
+// ---- ll, d ll / d (A_k, B_k) and d ll / d w01 at per-evaluation rates (nemo_grad.hip) ----
+static int rates_refusals(const Ctx& c) {
+  if (c.dtype != NEMO_F64)
+    return fail(NEMO_ERR_ARG, "nemo_score_rates: dtype f32 (NEMO_F32) context; the rates path is fp64 only (NEMO_F64)");
+  if (c.S > 64) return fail(NEMO_ERR_ARG, "nemo_score_rates: S=%d > 64 (the two-pass forward reads the staged U)", c.S);
+  if (!c.knockdown)
+    return fail(NEMO_ERR_STATE,
+                "nemo_score_rates: the model was not staged from a knockdown matrix (nemo_stage_knockdown); "
+                "generic and log-ratio tables have no error rates");
+  return NEMO_OK;
+}
+
+int nemo_score_rates_dev(nemo_ctx* ctx, int batch, const int32_t* d_pos, const double* d_w01, const double* d_rates,
+                         int cap, double* d_ll, double* d_drates, double* d_grad, void* stream) {
+  int rc = check_ctx(ctx, true);
+  if (rc) return rc;
+  Ctx& c = ctx->c;
+  if ((rc = rates_refusals(c))) return rc;
+  if (batch < 0 || cap < 0) return fail(NEMO_ERR_ARG, "batch=%d cap=%d", batch, cap);
+  if (batch == 0) return NEMO_OK;
+  if (batch > c.cap_batch) return fail(NEMO_ERR_STATE, "batch %d > reserved %d", batch, c.cap_batch);
+  if (!d_pos || !d_w01 || !d_rates || !d_ll || !d_drates) return fail(NEMO_ERR_ARG, "null device pointer");
+  if (!nemo::rates_ready(c)) return fail(NEMO_ERR_STATE, "nemo_score_rates: scratch not reserved");
+  HIPCHK(nemo::launch_score_rates(c, batch, cap, d_pos, d_w01, d_rates, d_ll, d_drates, d_grad, pick(ctx, stream)));
+  return NEMO_OK;
+}
+
+int nemo_score_rates(nemo_ctx* ctx, int batch, const int32_t* pos, const double* w01, const double* rates, int cap,
+                     double* ll_out, double* drates_out, double* grad_out) {
+  int rc = check_ctx(ctx, true);
+  if (rc) return rc;
+  Ctx& c = ctx->c;
+  if ((rc = rates_refusals(c))) return rc;
+  if (batch < 0 || cap < 0) return fail(NEMO_ERR_ARG, "batch=%d cap=%d", batch, cap);
+  if (batch == 0) return NEMO_OK;
+  if (!pos || !w01 || !rates || !ll_out || !drates_out) return fail(NEMO_ERR_ARG, "null host pointer");
+  if ((rc = check_pos(pos, batch, c.S))) return rc;
+  const size_t S = c.S, nr = (size_t)batch * 2 * S;
+  for (size_t k = 0; k < nr; ++k)
+    if (!isfinite(rates[k]) || fabs(rates[k]) > 700.0)
+      return fail(NEMO_ERR_ARG, "nemo_score_rates: rates[%zu][%c][%zu] = %g is not finite within [-700, 700]",
+                  k / (2 * S), (k / S) % 2 ? 'B' : 'A', k % S, rates[k]);
+  if ((rc = nemo_reserve(ctx, batch, 0))) return rc;
+  hipStream_t st = c.stream;
+  HIPCHK(hipMemcpyAsync(c.d_pos, pos, batch * S * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(c.d_w01, w01, batch * S * S * 8, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(c.d_rates, rates, nr * 8, hipMemcpyHostToDevice, st));
+  if ((rc = nemo_score_rates_dev(ctx, batch, c.d_pos, c.d_w01, c.d_rates, cap, c.d_ll, c.d_drates,
+                                 grad_out ? c.d_grad : nullptr, st)))
+    return rc;
+  HIPCHK(hipMemcpyAsync(ll_out, c.d_ll, batch * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(drates_out, c.d_drates, nr * 8, hipMemcpyDeviceToHost, st));
+  if (grad_out) HIPCHK(hipMemcpyAsync(grad_out, c.d_grad, batch * S * S * 8, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   return NEMO_OK;
 }

@@ -117,6 +117,36 @@ __global__ __launch_bounds__(256) void prep_factored_kernel(
   delta_row(S, SPAD, cap, b, q, perm, w01, e_lo, e_hi, Dp, G, tid & (kWave - 1));
 }
 
+// nemo_score_rates' prep (S <= 64): prep_factored_kernel with each evaluation's
+// own two values per parent row, e_lo = e^{B_j} (D[j][e] = 0) and e_hi =
+// e^{-A_j} (D[j][e] = 1), from rates [b][2][S] (A row, B row).  Every block
+// forms them in LDS; group 0 leaves them in rexp [b][2][S] (e^B row, e^-A row)
+// for the finish.
+__global__ __launch_bounds__(256) void prep_rates_kernel(
+    int S, int SPAD, int cap, const int32_t* __restrict__ pos, const double* __restrict__ w01,
+    const double* __restrict__ rates, double* __restrict__ Dp, double* __restrict__ G,
+    int32_t* __restrict__ permo, double* __restrict__ rexp) {
+  __shared__ int perm[kMaxS];
+  __shared__ int scan[kMaxS];
+  __shared__ double ev[2 * 64];
+  const int ngroups = SPAD / 4;
+  const int b = blockIdx.x / ngroups;
+  const int grp = blockIdx.x - b * ngroups;
+  const int tid = threadIdx.x;
+  if (tid < 2 * S) {
+    const int hi = tid >= S, j = tid - (hi ? S : 0);
+    const double* rb = rates + (size_t)b * 2 * S;
+    const double v = hi ? exp(-rb[j]) : exp(rb[S + j]);
+    ev[64 * hi + j] = v;
+    if (grp == 0) rexp[(size_t)b * 2 * S + tid] = v;
+  }
+  prep_order_lds(S, cap, pos + (size_t)b * S, perm, scan, false);  // (its barriers publish ev)
+  if (grp == 0)
+    for (int k = tid; k < SPAD; k += blockDim.x) permo[(size_t)b * SPAD + k] = k < S ? perm[k] : S;
+  const int q = 4 * grp + tid / kWave;
+  delta_row(S, SPAD, cap, b, q, perm, w01, ev, ev + 64, Dp, G, tid & (kWave - 1));
+}
+
 // the fused step's prep (nemo_optimal_weights_dev): prep_kernel's work for
 // children 4 g .. 4 g + 3 and prep_factored_kernel's for positions 4 g ..
 // 4 g + 3 in one block g of the evaluation -- the same arithmetic, one
@@ -532,6 +562,15 @@ hipError_t launch_prep_factored(Ctx& c, int batch, int cap, const int32_t* d_pos
   const int spad = c.fspad;
   prep_factored_kernel<<<batch * (spad / 4), 256, 0, st>>>(c.S, spad, cap, d_pos, d_w01, c.d_elo, c.d_ehi,
                                                            c.d_fDp, c.d_fG, c.d_fperm);
+  return hipGetLastError();
+}
+
+hipError_t launch_prep_rates(Ctx& c, int batch, int cap, const int32_t* d_pos, const double* d_w01,
+                             const double* d_rates, hipStream_t st) {
+  const int spad = c.fspad;
+  if (spad > 64 || !c.d_rexp) return hipErrorInvalidValue;
+  prep_rates_kernel<<<batch * (spad / 4), 256, 0, st>>>(c.S, spad, cap, d_pos, d_w01, d_rates, c.d_fDp, c.d_fG,
+                                                        c.d_fperm, c.d_rexp);
   return hipGetLastError();
 }
 

@@ -33,6 +33,10 @@
 // (t_begin + w, + kGradWaves, ...) into its accumulators, the block adds its
 // waves' accumulators in wave order through the LDS, and grad_finish_kernel
 // adds the parts in order.  The parts are a function of E alone (grad_parts).
+//
+// The same kernel with RATES set serves nemo_score_rates: the score at each
+// evaluation's own per-gene error rates with its derivatives in them, from M,
+// R and the diagonal M_kk (rates_finish_kernel below).
 #include "nemo_internal.h"
 
 #include <math.h>
@@ -75,12 +79,24 @@ __device__ __forceinline__ int clamp_pos(int p, int S) { return p < 0 ? 0 : (p >
 // fused: grid = batch * nparts (evaluation-major, XCD remap), block =
 // kGradWaves waves.  Mpart [b][part][tile (rq, rp), rq (rq + 1) / 2 + rp][reg][lane],
 // llpart [b][part].
+//
+// RATES (nemo_score_rates): the offset form at this evaluation's own rates.
+// D1w holds D's own bits (Ctx::d_Dw), Delta and G come from prep_rates_kernel,
+// and x[q][e] = cell - U[S][e] leaves the MFMA chain complete: its C-init is
+// the own term (D[q][e] ? -A_q : B_q; 0 on padding rows, whose G hides them),
+// picked by the child's own bit -- bit 4 g of pb[r], the second contraction's A
+// fragment.  No U is read and the null row is the constant 0; the finish adds
+// sum_k A_k n_k.  Each lane also sums ow[q][e] D[q][e], the diagonal M_qq that
+// d/dA_q and d/dB_q need: the diagonal tile holds it except at q = 15 mod 16,
+// where row 15 carries R; Dpart [b][part][SPAD] takes all of them.  The lane
+// sums live in per-wave LDS slots (one per lane and row block: no VGPR, which
+// NR = 4 has none to give, and no conflict).
 // ---------------------------------------------------------------------------
-template <int NR>
+template <int NR, bool RATES>
 __global__ __launch_bounds__(kGradWaves* kWave) void score_grad_fused_kernel(
     int S, int E, int ntiles, int nparts, const double* __restrict__ Dp, const int32_t* __restrict__ permo,
     const uint64_t* __restrict__ D1w, int nwords, const double* __restrict__ U, double* __restrict__ Mpart,
-    double* __restrict__ llpart, int remap) {
+    double* __restrict__ llpart, int remap, const double* __restrict__ rates, double* __restrict__ Dpart) {
   constexpr int SPAD = NR * 16;
   constexpr int LDA = SPAD + 2;  // == 2 mod 32: conflict-free b64 Delta fragments
   constexpr int NS = SPAD / 4;
@@ -94,6 +110,8 @@ __global__ __launch_bounds__(kGradWaves* kWave) void score_grad_fused_kernel(
   double* llw = (double*)(ltab + 128);             // [kGradWaves]
   double* A = llw + kGradWaves;                    // [SPAD][LDA], then the reduction's [NT][4][64]
   uint64_t* words = (uint64_t*)(A + SPAD * LDA);   // [NWB][SPAD] D1 words, word-major
+  double* own = (double*)(words + NWB * SPAD);     // RATES: [2][SPAD] own term by bit
+  double* dg = own + 2 * SPAD;                     // RATES: [kGradWaves][NR][64] each lane's share of M_qq
 
   const int work = gxcd_work_index((int)blockIdx.x, (int)gridDim.x, remap);
   const int b = work / nparts;
@@ -123,8 +141,20 @@ __global__ __launch_bounds__(kGradWaves* kWave) void score_grad_fused_kernel(
   // rows of U of this lane's NR child positions (S = the null row: padding)
   // (element offsets: (S + 1) E < 2^31 for S <= 64 at every E the staging takes)
   uint32_t urow[NR];
+  if constexpr (!RATES) {
 #pragma unroll
-  for (int r = 0; r < NR; ++r) urow[r] = (uint32_t)pm[16 * r + col] * (uint32_t)E;
+    for (int r = 0; r < NR; ++r) urow[r] = (uint32_t)pm[16 * r + col] * (uint32_t)E;
+  } else {
+    // own[0][q] = B of the node at position q, own[1][q] = -A of it
+    const double* rb = rates + (size_t)b * 2 * S;
+    for (int k = tid; k < 2 * SPAD; k += blockDim.x) {
+      const int bit = k / SPAD, q = k - bit * SPAD;
+      const int node = pm[q];
+      own[k] = node < S ? (bit ? -rb[node] : rb[S + node]) : 0.0;
+    }
+#pragma unroll
+    for (int r = 0; r < NR; ++r) dg[(w * NR + r) * kWave + lane] = 0.0;
+  }
   __syncthreads();
 
   f64x4 acc2[NT];
@@ -136,15 +166,25 @@ __global__ __launch_bounds__(kGradWaves* kWave) void score_grad_fused_kernel(
   for (int t = t_begin + w; t < t_end; t += kGradWaves) {
     // ---- cells^T of tile t: acc[r][g] = cell[q = 16 r + col][e = 16 t + 4 g + rg]
     f64x4 acc[NR];
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const int ec = min(t * 16 + 4 * g + rg, E - 1);
-#pragma unroll
-      for (int r = 0; r < NR; ++r) acc[r][g] = U[urow[r] + ec];
-    }
     const int uidx = ((t * 16) >> 6) - w_lo;
     const int bit0 = (t * 16) & 63;
     const uint64_t* wt = words + (size_t)uidx * SPAD;
+    if constexpr (!RATES) {
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const int ec = min(t * 16 + 4 * g + rg, E - 1);
+#pragma unroll
+        for (int r = 0; r < NR; ++r) acc[r][g] = U[urow[r] + ec];
+      }
+    } else {
+#pragma unroll
+      for (int r = 0; r < NR; ++r) {
+        const uint32_t ob = (uint32_t)(wt[16 * r + col] >> (bit0 + rg));
+        const double o0 = own[16 * r + col], o1 = own[SPAD + 16 * r + col];
+#pragma unroll
+        for (int g = 0; g < 4; ++g) acc[r][g] = ((ob >> (4 * g)) & 1u) ? o1 : o0;
+      }
+    }
 #pragma unroll
     for (int s = 0; s < NS; ++s) {
       const uint32_t bv = (uint32_t)((wt[4 * s + rg] >> (bit0 + col)) & 1ull);
@@ -169,7 +209,8 @@ __global__ __launch_bounds__(kGradWaves* kWave) void score_grad_fused_kernel(
     for (int g = 0; g < 4; ++g) {
       const int e = t * 16 + 4 * g + rg;
       const bool valid = e < E;
-      const double unull = U[(size_t)S * E + (valid ? e : E - 1)];
+      double unull = 0.0;
+      if constexpr (!RATES) unull = U[(size_t)S * E + (valid ? e : E - 1)];
       double m = acc[0][g];
 #pragma unroll
       for (int r = 1; r < NR; ++r) m = fmax(m, acc[r][g]);
@@ -183,6 +224,10 @@ __global__ __launch_bounds__(kGradWaves* kWave) void score_grad_fused_kernel(
       double ow[NR];
 #pragma unroll
       for (int r = 0; r < NR; ++r) ow[r] = valid ? exp_lse(acc[r][g] - cs, etab) : 0.0;
+      if constexpr (RATES) {
+#pragma unroll
+        for (int r = 0; r < NR; ++r) dg[(w * NR + r) * kWave + lane] += ((pb[r] >> (4 * g)) & 1u) ? ow[r] : 0.0;
+      }
 #pragma unroll
       for (int rp = 0; rp < NR; ++rp) {
         const uint32_t av = (pb[rp] >> (4 * g)) & 1u;
@@ -200,6 +245,15 @@ __global__ __launch_bounds__(kGradWaves* kWave) void score_grad_fused_kernel(
   // ---- the block's sums, waves in order (A's LDS reused once every wave is done with it)
   csum = gwave_sum(csum);
   if (lane == 0) llw[w] = csum;
+  if constexpr (RATES) {
+    // M_qq: the four row groups of a wave into its slots' first 16 lanes (the
+    // wave's own reads come first), then the waves in order below
+#pragma unroll
+    for (int r = 0; r < NR; ++r) {
+      const double v = rowsum4(dg[(w * NR + r) * kWave + lane]);
+      if (rg == 0) dg[(w * NR + r) * kWave + col] = v;
+    }
+  }
   double* red = A;
   for (int ww = 0; ww < kGradWaves; ++ww) {
     __syncthreads();
@@ -220,6 +274,13 @@ __global__ __launch_bounds__(kGradWaves* kWave) void score_grad_fused_kernel(
     double s = 0.0;
     for (int ww = 0; ww < kGradWaves; ++ww) s += llw[ww];
     llpart[(size_t)b * nparts + part] = s;
+  }
+  if constexpr (RATES) {
+    if (tid < SPAD) {
+      double s = 0.0;
+      for (int ww = 0; ww < kGradWaves; ++ww) s += dg[(ww * NR + (tid >> 4)) * kWave + (tid & 15)];
+      Dpart[((size_t)b * nparts + part) * SPAD + tid] = s;
+    }
   }
 }
 
@@ -258,6 +319,91 @@ __global__ __launch_bounds__(256) void grad_finish_kernel(
       g = fprime(w, e_lo[j]) * (r - m) + fprime(w, e_hi[j]) * m;
     }
     grad[(size_t)b * S * S + k] = g;
+  }
+}
+
+// nemo_score_rates' finish, grid and grad as grad_finish_kernel with this
+// evaluation's e^{B_j} / e^{-A_j} (rexp [b][2][S], prep_rates_kernel) in place
+// of the staged e_lo / e_hi; ll gains sum_k A_k n_k (strided lane sums, then the
+// xor tree).  One wave per gene k (blk * 4 + wave, + 4 nblk, ...): lane l takes
+// the child at position pos[k] + 1 + l -- the children in order position --
+//     dA_k = n_k - M_kk - sum_i h_ik M_ik,   dB_k = (R_k - M_kk) + sum_i k_ik (R_i - M_ik),
+// h = w e^{-A_k} / fma(w, e^{-A_k}, 1 - w), k = w e^{B_k} / fma(w, e^{B_k}, 1 - w): the
+// forward's own denominators.  R - M is a difference of two sums of the same
+// non-negative terms, as in g_ij: its error is relative to R, which the
+// tolerance carries.  drates [b][2][S]; grad may be null.
+__global__ __launch_bounds__(256) void rates_finish_kernel(
+    int S, int SPAD, int cap, int nparts, const int32_t* __restrict__ pos, const double* __restrict__ w01,
+    const int32_t* __restrict__ permo, const double* __restrict__ rates, const double* __restrict__ rexp,
+    const double* __restrict__ nk, const double* __restrict__ Mpart, const double* __restrict__ Dpart,
+    const double* __restrict__ llpart, double* __restrict__ ll, double* __restrict__ drates,
+    double* __restrict__ grad) {
+  const int nblk = (S * S + 255) / 256;
+  const int b = blockIdx.x / nblk, blk = blockIdx.x - b * nblk, tid = threadIdx.x;
+  const int lane = tid & (kWave - 1), wv = tid / kWave;
+  const int nr = SPAD / 16;
+  const size_t pd = (size_t)nr * (nr + 1) / 2 * 256;
+  const double* Mb = Mpart + (size_t)b * nparts * pd;
+  const double* Db = Dpart + (size_t)b * nparts * SPAD;
+  const double* ra = rates + (size_t)b * 2 * S;
+  const double* eB = rexp + (size_t)b * 2 * S;
+  const double* enA = eB + S;
+  // M[q][p] (p < q) and R[q], the parts in order
+  auto m_of = [&](int q, int p) {
+    const int rq = q >> 4, rp = p >> 4, c = q & 15, row = p & 15;
+    const size_t o = (size_t)(rq * (rq + 1) / 2 + rp) * 256 + (row >> 2) * kWave + (row & 3) * 16 + c;
+    double m = 0.0;
+    for (int t = 0; t < nparts; ++t) m += Mb[t * pd + o];
+    return m;
+  };
+  auto r_of = [&](int q) {
+    const int rq = q >> 4, c = q & 15;
+    const size_t o = (size_t)(rq * (rq + 1) / 2 + rq) * 256 + 3 * kWave + 48 + c;
+    double r = 0.0;
+    for (int t = 0; t < nparts; ++t) r += Mb[t * pd + o];
+    return r;
+  };
+  if (blk == 0 && tid < kWave) {
+    double base = 0.0;
+    for (int k = tid; k < S; k += kWave) base += ra[k] * nk[k];
+    base = gwave_sum(base);
+    const double s = sum_partials(llpart + (size_t)b * nparts, nparts, tid);
+    if (tid == 0) ll[b] = s + base;
+  }
+  const int32_t* pb = pos + (size_t)b * S;
+  const int k = blk * 256 + tid;
+  if (grad && k < S * S) {
+    const int i = k / S, j = k - i * S;
+    const int q = clamp_pos(pb[i], S), p = clamp_pos(pb[j], S);
+    double g = 0.0;
+    if (p < q && (cap == 0 || q - p <= cap)) {
+      const double m = m_of(q, p), r = r_of(q);
+      const double w = w01[(size_t)b * S * S + k];
+      g = fprime(w, eB[j]) * (r - m) + fprime(w, enA[j]) * m;
+    }
+    grad[(size_t)b * S * S + k] = g;
+  }
+  const int32_t* pm = permo + (size_t)b * SPAD;
+  for (int gene = blk * 4 + wv; gene < S; gene += nblk * 4) {
+    const int p = clamp_pos(pb[gene], S);
+    const int q = p + 1 + lane;
+    double ta = 0.0, tb = 0.0;
+    if (q < S && (cap == 0 || q - p <= cap)) {
+      const int i = pm[q];
+      const double m = m_of(q, p), r = r_of(q);
+      const double w = w01[((size_t)b * S + i) * S + gene];
+      const double s1 = 1.0 - w;
+      ta = w * enA[gene] / fma(w, enA[gene], s1) * m;
+      tb = w * eB[gene] / fma(w, eB[gene], s1) * (r - m);
+    }
+    ta = gwave_sum(ta);
+    tb = gwave_sum(tb);
+    if (lane == 0) {
+      double mkk = 0.0;
+      for (int t = 0; t < nparts; ++t) mkk += Db[t * SPAD + p];
+      drates[(size_t)b * 2 * S + gene] = nk[gene] - mkk - ta;
+      drates[(size_t)b * 2 * S + S + gene] = (r_of(p) - mkk) + tb;
+    }
   }
 }
 
@@ -308,16 +454,19 @@ __global__ __launch_bounds__(256) void grad_reduce_kernel(
   }
 }
 
-template <int NR>
-hipError_t launch_fused_t(Ctx& c, int batch, hipStream_t st) {
+template <int NR, bool RATES>
+hipError_t launch_fused_t(Ctx& c, int batch, hipStream_t st, const double* d_rates = nullptr) {
   constexpr int SPAD = NR * 16;
   const int ntiles = (c.E + 15) / 16;
   const int nparts = grad_parts(c.E);
   const size_t lds = (256 + 2 * 128 + kGradWaves) * 8 + (size_t)SPAD * (SPAD + 2) * 8 +
-                     (size_t)(kGradWaves * kGradTilesPerWave / 4) * SPAD * 8;
-  score_grad_fused_kernel<NR><<<dim3(batch * nparts), kGradWaves * kWave, lds, st>>>(
-      c.S, c.E, ntiles, nparts, c.d_fDp, c.d_fperm, c.d_D1w, c.nwords, (const double*)c.d_U64, c.d_gradM,
-      c.d_gradll, c.xcd_remap);
+                     (size_t)(kGradWaves * kGradTilesPerWave / 4) * SPAD * 8 +
+                     (RATES ? (size_t)(2 * SPAD + kGradWaves * NR * kWave) * 8 : 0);
+  static_assert((256 + 2 * 128 + kGradWaves + 64 * 66 + (kGradWaves * kGradTilesPerWave / 4) * 64 + 2 * 64 +
+                 kGradWaves * 4 * kWave) * 8 <= 65536, "the rates variant's LDS at NR = 4");
+  score_grad_fused_kernel<NR, RATES><<<dim3(batch * nparts), kGradWaves * kWave, lds, st>>>(
+      c.S, c.E, ntiles, nparts, c.d_fDp, c.d_fperm, RATES ? c.d_Dw : c.d_D1w, c.nwords,
+      RATES ? nullptr : (const double*)c.d_U64, c.d_gradM, c.d_gradll, c.xcd_remap, d_rates, c.d_rdiag);
   return hipGetLastError();
 }
 
@@ -330,14 +479,34 @@ hipError_t launch_score_grad_fused(Ctx& c, int batch, int cap, const int32_t* d_
   hipError_t err = launch_prep_factored(c, batch, cap, d_pos, d_w01, st);
   if (err != hipSuccess) return err;
   switch (c.fspad / 16) {
-    case 1: err = launch_fused_t<1>(c, batch, st); break;
-    case 2: err = launch_fused_t<2>(c, batch, st); break;
-    case 4: err = launch_fused_t<4>(c, batch, st); break;
+    case 1: err = launch_fused_t<1, false>(c, batch, st); break;
+    case 2: err = launch_fused_t<2, false>(c, batch, st); break;
+    case 4: err = launch_fused_t<4, false>(c, batch, st); break;
     default: return hipErrorInvalidValue;
   }
   if (err != hipSuccess) return err;
   grad_finish_kernel<<<batch * ((c.S * c.S + 255) / 256), 256, 0, st>>>(c.S, c.fspad, cap, grad_parts(c.E), d_pos, d_w01, c.d_elo, c.d_ehi,
                                             c.d_gradM, c.d_gradll, d_ll, d_grad);
+  return hipGetLastError();
+}
+
+hipError_t launch_score_rates(Ctx& c, int batch, int cap, const int32_t* d_pos, const double* d_w01,
+                              const double* d_rates, double* d_ll, double* d_drates, double* d_grad,
+                              hipStream_t st) {
+  if (!rates_ready(c) || c.dtype != 0 || c.fspad > 64) return hipErrorInvalidValue;
+  if (cap >= c.S - 1) cap = 0;  // a cap that cuts nothing (same lists, same bits)
+  hipError_t err = launch_prep_rates(c, batch, cap, d_pos, d_w01, d_rates, st);
+  if (err != hipSuccess) return err;
+  switch (c.fspad / 16) {
+    case 1: err = launch_fused_t<1, true>(c, batch, st, d_rates); break;
+    case 2: err = launch_fused_t<2, true>(c, batch, st, d_rates); break;
+    case 4: err = launch_fused_t<4, true>(c, batch, st, d_rates); break;
+    default: return hipErrorInvalidValue;
+  }
+  if (err != hipSuccess) return err;
+  rates_finish_kernel<<<batch * ((c.S * c.S + 255) / 256), 256, 0, st>>>(
+      c.S, c.fspad, cap, grad_parts(c.E), d_pos, d_w01, c.d_fperm, d_rates, c.d_rexp, c.d_nk, c.d_gradM, c.d_rdiag,
+      c.d_gradll, d_ll, d_drates, d_grad);
   return hipGetLastError();
 }
 

@@ -121,6 +121,19 @@ struct Ctx {
   double* d_gradM = nullptr;       // [cap][grad_parts][grad_part_doubles] the fused kernel's partial M tiles
   double* d_gradll = nullptr;      // [cap][grad_parts] its partial ll
 
+  // score and gradient in per-gene error rates (nemo_score_rates): what
+  // nemo_stage_knockdown keeps of D itself.  D's own words, not a flip flag per
+  // row over d_D1w: D1 is "not the row's first value" and a constant row stages
+  // no bits, so a flag would need a second one for "all ones"; the words are 16
+  // KB at 64 x 2000 and the kernel reads them as it reads d_D1w
+  bool knockdown = false;          // staged by nemo_stage_knockdown, S <= 64, fp64
+  uint64_t* d_Dw = nullptr;        // [S][nwords] bit D[k][e]
+  double* d_nk = nullptr;          // [S] n_k = sum_e D[k][e]
+  double* d_rexp = nullptr;        // [cap][2][S] e^{B_k} row, e^{-A_k} row of each evaluation
+  double* d_rdiag = nullptr;       // [cap][grad_parts][fspad] partial M_kk by order position
+  double* d_rates = nullptr;       // [cap][2][S] the host entry's rates
+  double* d_drates = nullptr;      // [cap][2][S] ... and their derivatives
+
   // the reference's own arithmetic in the fused step and the sampler's ll-only
   // calls (nemo_exact.hip): option "exact" (1 default), available when the
   // staged model is factored and numpy's pairwise sum of E fits the wave plan
@@ -660,6 +673,21 @@ inline bool grad_fused_shape(const Ctx& c) { return c.dtype == 0 && factored_spa
 // S <= 64); ll [batch], grad [batch][S][S] (every entry written)
 hipError_t launch_score_grad_fused(Ctx& c, int batch, int cap, const int32_t* d_pos, const double* d_w01,
                                    double* d_ll, double* d_grad, hipStream_t st);
+// ---- score and gradient in per-gene error rates (nemo_score_rates) ----
+// d_rates [batch][2][S] (A_k row, B_k row); the scratch of nemo_reserve holds
+// the batch and the model was staged from a knockdown matrix
+inline bool rates_ready(const Ctx& c) {
+  return c.knockdown && c.d_Dw && c.d_nk && c.d_rexp && c.d_rdiag && c.d_gradM && c.d_gradll;
+}
+// prep_rates_kernel: prep_factored_kernel's Delta / G / perm with e_lo = e^{B_j},
+// e_hi = e^{-A_j} of each evaluation (also left in d_rexp for the finish)
+hipError_t launch_prep_rates(Ctx& c, int batch, int cap, const int32_t* d_pos, const double* d_w01,
+                             const double* d_rates, hipStream_t st);
+// prep, the fused kernel's rates variant and its finish: ll [batch], drates
+// [batch][2][S], grad [batch][S][S] (nullable; every entry written)
+hipError_t launch_score_rates(Ctx& c, int batch, int cap, const int32_t* d_pos, const double* d_w01,
+                              const double* d_rates, double* d_ll, double* d_drates, double* d_grad,
+                              hipStream_t st);
 // the two-pass path's second pass: the reduction over (evaluation, child,
 // parent) of the order weights d_ow [batch][S+1][E] against the D1 bits
 // (factored) or the staged exp(T) rows (generic, fp64)

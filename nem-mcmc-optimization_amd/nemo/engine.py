@@ -210,6 +210,38 @@ class Engine:
         the batch first)."""
         check(_lib.load().nemo_score_grad_dev(self._ctx, int(batch), d_pos, d_w01, int(cap), d_ll, d_grad, stream))
 
+    # -- the error rates as parameters ------------------------------------------
+    def score_rates(self, pos, w01, A, B, cap: int = 0, want_grad_w: bool = True):
+        """Order scores at per-gene error rates, with their derivatives, on an
+        engine made by ``from_knockdown`` (fp64, S <= 64): nothing is restaged.
+
+        ``A``, ``B``: A_k = log(alpha_k / (1 - beta_k)) and B_k = log(beta_k /
+        (1 - alpha_k)), each a scalar, (S,) or (batch, S).  Returns (ll (B,),
+        dA (B, S), dB (B, S), grad (B, S, S) or None): d ll / d A_k, d ll /
+        d B_k and d ll / d w01 (exactly 0 off the permissible pairs; w01 is
+        not read there).  ``nemo.rates.absolute_ll`` adds the baseline that
+        makes ll comparable across rates."""
+        pos = i32(np.atleast_2d(pos))
+        b = pos.shape[0]
+        w01 = f64(w01).reshape(b, self.S, self.S)
+        rates = np.empty((b, 2, self.S))
+        rates[:, 0] = np.broadcast_to(np.asarray(A, dtype=np.float64), (b, self.S))
+        rates[:, 1] = np.broadcast_to(np.asarray(B, dtype=np.float64), (b, self.S))
+        ll = np.empty(b)
+        dr = np.empty((b, 2, self.S))
+        grad = np.empty((b, self.S, self.S)) if want_grad_w else None
+        a = _lib.addr
+        check(_lib.load().nemo_score_rates(self._ctx, b, a(pos), a(w01), a(rates), int(cap), a(ll), a(dr),
+                                           None if grad is None else a(grad)))
+        return ll, dr[:, 0].copy(), dr[:, 1].copy(), grad
+
+    def score_rates_dev(self, batch, d_pos, d_w01, d_rates, d_ll, d_drates, d_grad=None, cap=0, stream=None):
+        """Enqueue ``score_rates`` on device pointers (no sync; ``reserve`` the
+        batch first): rates and drates are (batch, 2, S), the A row then the B
+        row; ``d_grad`` may be None."""
+        check(_lib.load().nemo_score_rates_dev(self._ctx, int(batch), d_pos, d_w01, d_rates, int(cap), d_ll,
+                                               d_drates, d_grad, stream))
+
     # -- utils.compute_ll / calculate_ll on a given cell matrix ------------
     def lse(self, cells, want_ow=False):
         cells = f64(cells)
