@@ -54,6 +54,17 @@
 #ifndef NEMO_I8L_PINGPONG
 #define NEMO_I8L_PINGPONG 1
 #endif
+// score_i8l_kernel's two-tile walk, the issue order of a row block: phases
+// the scheduler may not merge, the next row block's A fragments and G C-inits
+// requested behind the table reads, the B prefetch in the last row block (1),
+// or whatever order the compiler picks (0: it pools the MFMAs of several row
+// blocks and waits on each table read right after issuing it; the same bits).
+// Needs NEMO_I8L_RINIT; S <= 16 (one row block) keeps 0.  score_i8p_kernel
+// keeps 0 too: the requested fragments would be live across its hook (the
+// next evaluation's prep), which spills.
+#ifndef NEMO_I8L_SCHED
+#define NEMO_I8L_SCHED 1
+#endif
 // register budget: waves per SIMD the int8 score kernel is compiled for
 #ifndef NEMO_I8_WAVES_PER_SIMD
 #define NEMO_I8_WAVES_PER_SIMD 2
@@ -1063,8 +1074,9 @@ hipError_t launch_i8o_t(Ctx& c, int batch, int cap, const int32_t* d_pos, const 
 // one evaluation (A fragments Al, G C-inits Gi, partials of evaluation b).
 // hook(it) runs between iterations it and it + 1 (it = 0, 1, ...) and returns
 // nothing the walk reads: score_i8p_kernel runs the next evaluation's digit
-// prep there.  Returns the number of iterations walked.
-template <int NR, int WAVES, bool PP, class Hook>
+// prep there.  Returns the number of iterations walked.  SCHED: the row
+// blocks in enforced phases (NEMO_I8L_SCHED; i8l_rowblocks_sched below).
+template <int NR, int WAVES, bool PP, bool SCHED, class Hook>
 __device__ __forceinline__ int i8l_walk2(const i32x4* __restrict__ Al0, const i32x4* __restrict__ Gi,
                                         const i32x4* __restrict__ Bt, const i32x4* __restrict__ Bt64,
                                         int set, int s_end, int ntiles, int E, int col, int lane,
@@ -1092,6 +1104,115 @@ __device__ __forceinline__ int i8l_walk2(const i32x4* __restrict__ Al0, const i3
     };
     i32x4 bca = bload(t, 0), bca64 = bload(t, 1);
     i32x4 bcb = bload(t2, 0), bcb64 = bload(t2, 1);
+    // SCHED: the row blocks of one iteration in phases that the scheduler may
+    // not merge (sched_barrier), each LDS read issued a phase or more ahead of
+    // its use.  Left alone the scheduler pools the MFMAs of three row blocks
+    // ahead of every epilogue, and with their T_0 and R live has no register
+    // left for a table entry in flight: read, wait, use, 32 times over.
+    //   1  the MFMAs of slices 0-3 and 5-6 (the last row block first requests
+    //      the next iteration's B fragments: an L2 hit, due in a few hundred
+    //      cycles, not live for the whole iteration)
+    //   2  T_0 and slice 4's C-init for the 8 cells, then slice 4's MFMAs
+    //      (slices 5-6 cover T_0's wait on the matrix core)
+    //   3  the 8 table addresses and reads (they cover slice 4's result), and
+    //      behind them the request for the next row block's slices 0-3 and
+    //      T_0's C-init: LDS returns in order, so the waits on the table
+    //      entries are counted ones that leave the requests in flight
+    //   4  R, its conversion and the series for the 8 cells: 32 VALU, the
+    //      cover of the table reads; then the request for slices 4-6 and T_1's
+    //      C-init, into the registers R leaves
+    //   5  the entries applied and accumulated
+    // fa / fc0 / fc1 hold the requested row block; row block 0's come from the
+    // last row block of the iteration before, across a set finish and the
+    // hook (A and G are the evaluation's: the same in every iteration).
+    // The arithmetic of every cell and the order of every sum are the
+    // unscheduled loop's, so the bits are.
+    i32x4 fa[7], fc0, fc1;
+    // (in two groups: all nine in flight next to the table entries, T_0 and
+    // T_1 spill)
+    auto request_hi = [&](const i32x4* Al, int r) {
+#pragma unroll
+      for (int sl = 0; sl < 4; ++sl) fa[sl] = Al[(sl * SPAD + 16 * r) * 4];
+      fc0 = Gi[(16 * r) / 4 + rg];
+    };
+    auto request_lo = [&](const i32x4* Al, int r) {
+#pragma unroll
+      for (int sl = 4; sl < 7; ++sl) fa[sl] = Al[(sl * SPAD + 16 * r) * 4];
+      fc1 = Gi[(SPAD + 16 * r) / 4 + rg];
+    };
+    if constexpr (SCHED) {
+      request_hi(Al0 + a_lane, 0);
+      request_lo(Al0 + a_lane, 0);
+    }
+    auto pin = [](i32x4& v) { asm volatile("" : "+v"(v)); };
+    auto i8l_rowblocks_sched = [&](const i32x4 b1a, const i32x4 b64a, const i32x4 b1b, const i32x4 b64b,
+                                   const i32x4* Al, double& la0, double& la1, double& lb0, double& lb1,
+                                   auto&& bprefetch) {
+#pragma unroll
+      for (int r = 0; r < NR; ++r) {
+        if (r == NR - 1) bprefetch();
+        const i32x4 z = i32x4{0, 0, 0, 0};
+        i32x4 h0a = __builtin_amdgcn_mfma_i32_16x16x64_i8(fa[0], b64a, z, 0, 0, 0);
+        i32x4 h0b = __builtin_amdgcn_mfma_i32_16x16x64_i8(fa[0], b64b, z, 0, 0, 0);
+        h0a = __builtin_amdgcn_mfma_i32_16x16x64_i8(fa[1], b1a, h0a, 0, 0, 0);
+        h0b = __builtin_amdgcn_mfma_i32_16x16x64_i8(fa[1], b1b, h0b, 0, 0, 0);
+        i32x4 h1a = __builtin_amdgcn_mfma_i32_16x16x64_i8(fa[2], b64a, fc0, 0, 0, 0);
+        i32x4 h1b = __builtin_amdgcn_mfma_i32_16x16x64_i8(fa[2], b64b, fc0, 0, 0, 0);
+        h1a = __builtin_amdgcn_mfma_i32_16x16x64_i8(fa[3], b1a, h1a, 0, 0, 0);
+        h1b = __builtin_amdgcn_mfma_i32_16x16x64_i8(fa[3], b1b, h1b, 0, 0, 0);
+        i32x4 l1a = __builtin_amdgcn_mfma_i32_16x16x64_i8(fa[5], b64a, fc1, 0, 0, 0);
+        i32x4 l1b = __builtin_amdgcn_mfma_i32_16x16x64_i8(fa[5], b64b, fc1, 0, 0, 0);
+        l1a = __builtin_amdgcn_mfma_i32_16x16x64_i8(fa[6], b1a, l1a, 0, 0, 0);
+        l1b = __builtin_amdgcn_mfma_i32_16x16x64_i8(fa[6], b1b, l1b, 0, 0, 0);
+        // (an MFMA has no side effect, so instruction selection places it with
+        // its first user, behind the barrier: the empty asm is a user in front)
+        pin(h0a), pin(h0b), pin(h1a), pin(h1b), pin(l1a), pin(l1b);
+        __builtin_amdgcn_sched_barrier(0);
+        uint32_t t0a[4], t0b[4];
+        i32x4 ma, mb;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          t0a[g] = ((uint32_t)h0a[g] << 12) + (uint32_t)h1a[g];
+          ma[g] = i8l_cinit16(t0a[g]);
+        }
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          t0b[g] = ((uint32_t)h0b[g] << 12) + (uint32_t)h1b[g];
+          mb[g] = i8l_cinit16(t0b[g]);
+        }
+        i32x4 l0a = __builtin_amdgcn_mfma_i32_16x16x64_i8(fa[4], b1a, ma, 0, 0, 0);
+        i32x4 l0b = __builtin_amdgcn_mfma_i32_16x16x64_i8(fa[4], b1b, mb, 0, 0, 0);
+        pin(l0a), pin(l0b);
+        __builtin_amdgcn_sched_barrier(0);
+        uint64_t eva[4], evb[4];
+#pragma unroll
+        for (int g = 0; g < 4; ++g) eva[g] = exp2_fx_load(t0a[g]);
+#pragma unroll
+        for (int g = 0; g < 4; ++g) evb[g] = exp2_fx_load(t0b[g]);
+        __builtin_amdgcn_sched_barrier(0);
+        request_hi(Al, r + 1 < NR ? r + 1 : 0);
+        __builtin_amdgcn_sched_barrier(0);
+        double pa[4], pb[4];
+#pragma unroll
+        for (int g = 0; g < 4; ++g) pa[g] = exp2_fx_series_r((int)(((uint32_t)l0a[g] << 11) + (uint32_t)l1a[g]));
+#pragma unroll
+        for (int g = 0; g < 4; ++g) pb[g] = exp2_fx_series_r((int)(((uint32_t)l0b[g] << 11) + (uint32_t)l1b[g]));
+        __builtin_amdgcn_sched_barrier(0);
+        request_lo(Al, r + 1 < NR ? r + 1 : 0);  // T_1 is consumed: its registers take the second group
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          if (g & 1) la1 = exp2_fx_apply(t0a[g], eva[g], pa[g], la1);
+          else la0 = exp2_fx_apply(t0a[g], eva[g], pa[g], la0);
+        }
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          if (g & 1) lb1 = exp2_fx_apply(t0b[g], evb[g], pb[g], lb1);
+          else lb0 = exp2_fx_apply(t0b[g], evb[g], pb[g], lb0);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    };
     // one iteration on the fragments (b1a, b64a, b1b, b64b), prefetching the
     // next iteration's into (na, na64, nb, nb64); false after the last
     auto iter = [&](const i32x4 b1a, const i32x4 b64a, const i32x4 b1b, const i32x4 b64b, i32x4& na,
@@ -1108,11 +1229,21 @@ __device__ __forceinline__ int i8l_walk2(const i32x4* __restrict__ Al0, const i3
       const bool more = setn < s_end;
       const int tla = __builtin_amdgcn_readfirstlane(more ? tn : t);
       const int tlb = __builtin_amdgcn_readfirstlane(more ? (tn + 1 < tend(setn) ? tn + 1 : tn) : t);
-      na = bload(tla, 0);
-      na64 = bload(tla, 1);
-      nb = bload(tlb, 0);
-      nb64 = bload(tlb, 1);
+      if constexpr (!SCHED) {
+        na = bload(tla, 0);
+        na64 = bload(tla, 1);
+        nb = bload(tlb, 0);
+        nb64 = bload(tlb, 1);
+      }
       double la0 = 0.0, la1 = 0.0, lb0 = 0.0, lb1 = 0.0;
+      if constexpr (SCHED) {
+        i8l_rowblocks_sched(b1a, b64a, b1b, b64b, Al, la0, la1, lb0, lb1, [&] {
+          na = bload(tla, 0);
+          na64 = bload(tla, 1);
+          nb = bload(tlb, 0);
+          nb64 = bload(tlb, 1);
+        });
+      } else
 #pragma unroll
       for (int r = 0; r < NR; ++r) {
         const i32x4 c0 = Gi[(16 * r) / 4 + rg];
@@ -1443,8 +1574,10 @@ __global__ __launch_bounds__(WAVES * kWave, OCC) void score_i8l_kernel(
     // arithmetic per cell and the same order of the column products as TT = 1,
     // so the same bits.  The second tile of a set's odd tail repeats the first
     // and is not multiplied in.
-    i8l_walk2<NR, WAVES, NEMO_I8L_PINGPONG != 0>(ev.A, Gi, Bt, Bt64, set, s_end, ntiles, E, col, lane, a_lane,
-                                                 nullsum, partial, b, nsets, ltab, [](int) {});
+    // (one row block has nothing to pool, and the phases cost it 0.7%)
+    constexpr bool kSched = NEMO_I8L_SCHED != 0 && NEMO_I8L_RINIT != 0 && NR > 1;
+    i8l_walk2<NR, WAVES, NEMO_I8L_PINGPONG != 0, kSched>(ev.A, Gi, Bt, Bt64, set, s_end, ntiles, E, col, lane,
+                                                         a_lane, nullsum, partial, b, nsets, ltab, [](int) {});
   }
   if (split == 1) {
     __syncthreads();
@@ -1722,7 +1855,7 @@ __global__ __launch_bounds__(WAVES * kWave, NEMO_I8L2_OCC) void score_i8p_kernel
   for (int e = b0; e < batch; e += nb, k ^= 1) {
     const int en = e + nb;
     bool pending = en < batch;
-    i8l_walk2<NR, WAVES, false>(evb(k).A, (const i32x4*)gib(k), Bt, Bt64, w, nsets, ntiles, E, col, lane, a_lane,
+    i8l_walk2<NR, WAVES, false, false>(evb(k).A, (const i32x4*)gib(k), Bt, Bt64, w, nsets, ntiles, E, col, lane, a_lane,
                          nullsum, partial, (size_t)e, nsets, ltab, [&](int it) {
                            if (pending && it == 0) {
                              prep(k ^ 1, en);
