@@ -70,8 +70,21 @@ const char* nemo_build_id(void);
 /* number of visible HIP devices (0 on a host without GPU; never an error) */
 int nemo_device_count(int* count);
 
+/* option "exact_generic": the largest |T| (off-diagonal rows) and |U| of a
+ * generic or row-shared table the exact kernels cover.  U only has to stay
+ * inside the SVML exp's fast path.  T is bounded so that a flushed order
+ * weight (see "exact") cannot change a local optimum: c = a / b with a =
+ * (lv - 1) ow, b = (1 - s) + s lv - s a, lv = e^T, so for a tail weight ow <=
+ * e^-707.70 |c| <= max(lv, 1) / min(lv, 1) * e^-707.70 = e^(|T| - 707.70),
+ * and 1 + c ex (ex in [0, 1]) is 1 with ow or with 0 once |c| < 2^-54 =
+ * e^-37.43: |T| <= 670.27, rounded down (nemo.limits holds the same values) */
+#define NEMO_EXACT_GENERIC_MAX_ABS_T 670.0
+#define NEMO_EXACT_GENERIC_MAX_ABS_U 700.0
+
 /* ---- context lifetime (replaces NEMOrderMCMC.__init__'s table setup,
- *      nem_order_mcmc.py:40-46) ------------------------------------------ */
+ *      nem_order_mcmc.py:40-46) ------------------------------------------
+ * num_s in [2, 256] (a model of one S-gene has no parent pair: num_s = 1 is
+ * NEMO_ERR_ARG), num_e >= 1 */
 int nemo_ctx_create(int device, int num_s, int num_e, int dtype, nemo_ctx** out);
 void nemo_ctx_destroy(nemo_ctx* ctx);
 /* grow per-batch scratch so *_dev calls with up to max_batch evaluations
@@ -392,7 +405,17 @@ int nemo_real_sweep(nemo_ctx* ctx, int nprob, const int32_t* pos, const double* 
  *                (csrc/refmath.h, csrc/lbfgsb_exact.h, csrc/nemo_exact.hip):
  *                the same order scores, order weights, local optima and
  *                weights as nem_order_mcmc.py, to the bit, when "exact_ok";
- *                0 = the fast kernels (scores within ~1e-9)
+ *                0 = the fast kernels (scores within ~1e-9).
+ *                One exception, in the order weights only: np.exp is restated
+ *                on its fast path, |x| < 707.70 (0x1.61da04cbafe44p+9), so an
+ *                order weight exp(cell - cs) of a cell more than 707.70 below
+ *                its column's log-sum is exactly 0.0 where numpy's rare path
+ *                gives 5e-324 .. 4.6e-308 (ll, cs and the cells are not
+ *                affected).  The local optima keep the reference's bits all
+ *                the same: such a weight enters c = a / b with |c| <=
+ *                e^(|T| - 707.70), and 1 + c ex = 1 with it or with 0 -- for
+ *                factored tables always (|T| <= 170), for generic ones by the
+ *                bound on |T| below (tests/test_exact_edges_cpu.py)
  *   "exact_dev"  0 (default): nemo_score_dev runs the fast kernels; 1 = the
  *                same conditions as "exact" on nemo_score, on device buffers
  *                (cells built in d_ow -- then order weights in place -- or in
@@ -400,14 +423,18 @@ int nemo_real_sweep(nemo_ctx* ctx, int nprob, const int32_t* pos, const double* 
  *   "exact_ok"   (get only) 1 if the staging supports "exact": factored
  *                tables, any parent cap, E <= 524288 (numpy's np.sum adds
  *                buffers of 8192 terms in order, each summed pairwise, and
- *                the local optima run one wave plan per buffer); or, with
+ *                the local optima run one wave plan per buffer -- of at most
+ *                64 leaf blocks: 441 buffer sizes in 7689 .. 8191, 8191 among
+ *                them, split into 65 and have no plan, "exact_ok" 0 for such
+ *                an E or last buffer; nemo.limits); or, with
  *                "exact_generic", a generic table within that option's bounds
  *   "exact_generic" 0 (default); 1 = nemo_stage_tables also stages a table
  *                that is not factorable (real-valued rows, e.g. per-effect
  *                log-likelihood ratios) for the exact kernels: np.exp(T) in
  *                numpy's bits in its own fp64 buffer and the wave plan of E.
- *                Covered ("exact_ok" 1) when max|T| (off-diagonal rows), max|U|
- *                <= 700 and
+ *                Covered ("exact_ok" 1) when max|T| (off-diagonal rows) <=
+ *                670 (NEMO_EXACT_GENERIC_MAX_ABS_T: a flushed order weight
+ *                cannot change a local optimum), max|U| <= 700 and
  *                  - a table with its own rows per child: E <= 8192 (one numpy
  *                    buffer); X is [S][S][E] and the local optima read stored
  *                    c rows ("exact_form" 1 or 2 -- a form that needs the

@@ -442,8 +442,18 @@ int stage_factored(nemo_ctx* ctx, bool fact, const std::vector<uint64_t>& d1,
 // option exact_generic: the exact path's tables of a generic (not factorable)
 // model, from its fp64 table still on the device: X = np.exp(T) in numpy's
 // bits in its own buffer (the fast path's exp table is untouched) and the wave
-// plan of numpy's pairwise sum of E.  Covered (c.xg_ok): max|T| (the
-// off-diagonal rows, amax), max|U| <= 700, inside the SVML exp's fast path, and
+// plan of numpy's pairwise sum of E.  Covered (c.xg_ok): max|U| <= 700
+// (NEMO_EXACT_GENERIC_MAX_ABS_U), inside the SVML exp's fast path; max|T| (the
+// off-diagonal rows, amax) <= 670 (NEMO_EXACT_GENERIC_MAX_ABS_T), so that an
+// order weight the restated np.exp flushes to 0.0 (cell - cs < -707.70; numpy:
+// at most e^-707.70) cannot change a local optimum.  Such a weight ow of the
+// parent's row enters c = a / b, a = (lv - 1) ow, b = (1 - s) + s lv - s a, lv
+// = e^T: |a| <= max(lv, 1) e^-707.70 and b >= min(lv, 1) (1 - tiny), so |c| <=
+// e^(|T| - 707.70).  The objective reads c only in 1 + c ex, ex in [0, 1],
+// which rounds to 1 for |c| < 2^-54 = e^-37.43 -- with numpy's ow or with 0 --
+// hence |T| <= 707.70 - 37.43 = 670.27, rounded down.  (At |T| = 700, s ~
+// e^-700 the reference's c is e^-8 / 2 where the flushed one is 0:
+// tests/test_exact_edges_cpu.py.)  And
 //   * a table with its own rows per child: E <= 8192 -- one numpy buffer, the
 //     stored c rows serve one plan part;
 //   * a row-shared table (`shared`, host::detect_row_shared): E within the
@@ -461,9 +471,9 @@ int stage_exact_generic(Ctx& c, const double* d_t64, double amax, const double* 
       HIPCHK(hipFree(*p));
       *p = nullptr;
     }
-  if (!c.exact_generic || (!shared && E > 8192) || !(amax <= 700.0)) return NEMO_OK;
+  if (!c.exact_generic || (!shared && E > 8192) || !(amax <= NEMO_EXACT_GENERIC_MAX_ABS_T)) return NEMO_OK;
   for (size_t k = 0; k < (S + 1) * E; ++k)
-    if (!(fabs(U[k]) <= 700.0)) return NEMO_OK;
+    if (!(fabs(U[k]) <= NEMO_EXACT_GENERIC_MAX_ABS_U)) return NEMO_OK;
   std::vector<nemo::host::PairwisePlan> parts;
   if (!nemo::host::build_pairwise_parts(c.E, parts) || parts.size() > (size_t)nemo::kExactMaxParts ||
       (!shared && parts.size() != 1))
@@ -546,7 +556,7 @@ static int stage_tables(nemo_ctx* ctx, const double* U, const double* T, const d
   // the product range: four factors of the fast kernels' products stay finite.
   // Option exact_generic: a generic fp64 table may reach past it (a wide
   // table, nemo_internal.h) -- the exact kernels take no products (covered to
-  // 700), score_kernel renormalises every factor of such a table, and the
+  // NEMO_EXACT_GENERIC_MAX_ABS_T), score_kernel renormalises every factor of such a table, and the
   // other fast kernels that read exp(T) refuse it (refuse_wide)
   const double lim = c.dtype == NEMO_F64 ? nemo::kProductRangeF64 : nemo::kProductRangeF32;
   const bool wide = amax > lim && generic && c.exact_generic && c.dtype == NEMO_F64 && amax <= nemo::kWideTableMax;
@@ -692,8 +702,8 @@ static int refuse_wide(const Ctx& c, const char* what) {
   if (!nemo::wide_table(c)) return NEMO_OK;
   return fail(NEMO_ERR_ARG,
               "%s: |T| up to %g is past the fp64 product range (%g); such a table runs the exact kernels "
-              "(option exact_generic, |T| <= 700) and the score calls only",
-              what, c.table_absmax, nemo::kProductRangeF64);
+              "(option exact_generic, |T| <= %g) and the score calls only",
+              what, c.table_absmax, nemo::kProductRangeF64, (double)NEMO_EXACT_GENERIC_MAX_ABS_T);
 }
 
 // ---------------------------------------------------------------------------

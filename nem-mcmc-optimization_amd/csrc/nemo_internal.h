@@ -190,8 +190,10 @@ struct Ctx {
   int xtrace_n = 0;                // optima the last traced launch recorded
   // option "exact_generic" (0 default; set before staging): nemo_stage_tables
   // also stages a generic (not factorable) table for the exact kernels -- X =
-  // np.exp(T) in numpy's bits and the wave plan of E -- when max|T|, max|U| <=
-  // 700 (inside the SVML exp's fast path) and E <= 8192 (one numpy buffer: the
+  // np.exp(T) in numpy's bits and the wave plan of E -- when max|U| <= 700
+  // (inside the SVML exp's fast path), max|T| <= 670 (a flushed order weight
+  // cannot change a local optimum: nemo.h NEMO_EXACT_GENERIC_MAX_ABS_T,
+  // stage_exact_generic) and E <= 8192 (one numpy buffer: the
   // stored c rows serve one plan part), or, for a row-shared table (xg_shared),
   // E within the factored model's plans (kExactMaxParts buffers)
   int exact_generic = 0;

@@ -402,10 +402,19 @@ NEMO_RM double svml_log(double x, const TB& tb = TB{}) {
 // round-to-nearest fma and the sign of its residual), kf = t - S on a 1/16
 // grid, j its fraction, r = x - kf ln2 (two fused steps), degree-6
 // polynomial, 2^(j/16) (1 + p) scaled by 2^floor(kf).  |x| < 707.70 (the
-// library's fast path); below -707.70 the library's rare path gives a tiny
-// or zero result, here 0 (the path's only np.exp of such arguments are
-// order weights exp(cell - cs) of negligible rows, whose c = a / b then
-// enters log(c e + 1) as 1 + tiny = 1 either way).
+// library's fast path, the bound 0x1.61da04cbafe44p+9 below); at or below
+// -707.70 the library's rare path gives a tiny result (5e-324 .. 4.6e-308 down
+// to -745.13, then 0), here exactly 0.0; at or above +707.70 here inf, where
+// numpy is finite up to 709.78.  The rare path is an algorithm of its own
+// (neither glibc's exp nor this one continued) and is not restated.
+// Documented exception (include/nemo.h, option "exact"): the path's only
+// np.exp of such arguments are order weights exp(cell - cs) of cells more
+// than 707.70 below their column's log-sum -- those are 0.0 on the device,
+// not numpy's bits.  Everything computed from them keeps the reference's bits:
+// such a weight enters c = a / b with |c| <= e^(|T| - 707.70), and log(c e +
+// 1) reads 1 + tiny = 1 either way while |T| <= 670 -- factored tables have
+// |T| <= 170, generic ones are gated at 670 (stage_exact_generic;
+// tests/test_exact_edges_cpu.py, tests/test_gpu_exact_edges.py).
 // ---------------------------------------------------------------------------
 template <class TB = ConstTabs>
 NEMO_RM double svml_exp(double x, const TB& tb = TB{}) {

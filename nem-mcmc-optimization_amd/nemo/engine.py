@@ -34,8 +34,9 @@ class Engine:
 
     ``exact_generic=True`` (option ``exact_generic``, set before staging):
     real-valued tables that are not factorable are staged for the
-    reference-arithmetic kernels too -- covered for max|T|, max|U| <= 700 and
-    E <= 8192, or E <= 524288 when every child shares parent j's row
+    reference-arithmetic kernels too -- covered for max|T| <= 670, max|U| <=
+    700 (``nemo.limits``) and E <= 8192, or E <= 524288 when every child shares
+    parent j's row
     (``from_log_ratios``; ``exact_status``); a factorable table is unaffected.
     """
 
@@ -405,8 +406,10 @@ class Engine:
         # the library's own verdict on the staging (the wave plan it built)
         if ok and not self.get_option("exact_ok"):
             if not self.factored:
+                from .limits import MAX_ABS_T_EXACT_GENERIC, MAX_ABS_U_EXACT_GENERIC
                 return False, ("table form: the staged generic table is outside option exact_generic's bounds "
-                               "(max|T| and max|U| <= 700); the fast kernels")
+                               f"(max|T| <= {MAX_ABS_T_EXACT_GENERIC:g} and max|U| <= {MAX_ABS_U_EXACT_GENERIC:g}); "
+                               "the fast kernels")
             return False, f"E={self.E}: the staging found no wave plan for numpy's pairwise sum; the fast kernels"
         return ok, why
 

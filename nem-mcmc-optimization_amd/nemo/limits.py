@@ -28,10 +28,14 @@ MAX_E_FAST_LOCAL_OPT = 80 * 64
 NUMPY_BUFSIZE = 8192      # np.getbufsize(): np.sum adds buffer-sized chunks in order
 MAX_PARTS = 64            # csrc/nemo_internal.h kExactMaxParts
 # option exact_generic (csrc/nemo_abi.cpp stage_exact_generic): one numpy
-# buffer -- the stored c rows serve one wave plan -- and tables inside the
-# SVML exp's fast path
+# buffer -- the stored c rows serve one wave plan -- U inside the SVML exp's
+# fast path, and T where an order weight the restated np.exp flushes to 0.0
+# (cell - cs < -707.70) cannot change a local optimum: |c| <= e^(|T| - 707.70)
+# < 2^-54, so 1 + c ex = 1 either way (include/nemo.h
+# NEMO_EXACT_GENERIC_MAX_ABS_T / _U: the same two values, tests/test_limits.py)
 MAX_E_EXACT_GENERIC = NUMPY_BUFSIZE
-MAX_ABS_EXACT_GENERIC = 700.0
+MAX_ABS_T_EXACT_GENERIC = 670.0
+MAX_ABS_U_EXACT_GENERIC = 700.0
 
 
 def pairwise_parts(E: int):
@@ -83,25 +87,33 @@ def exact_limits(S: int, E: int, factored: bool, cap: int = 0, host_blas: str | 
     ``exact_shared``) -- covered over the factored model's range of E."""
     leaves = pairwise_leaves(E)
     parts = pairwise_parts(E)
+    # every buffer's pairwise recursion must fit the wave plan's 64 leaf blocks:
+    # 441 sizes in 7689 .. 8191 split into 65 (8191 = 4088 + 4103 -> ... -> 135 =
+    # 64 + 71), and the staging builds no plan for them (exact_ok 0)
+    e_covered = parts is not None and all(pairwise_leaves(n) <= MAX_LEAVES for n in parts)
     if exact_generic and row_shared:
         table_form = Limit(
             "table form", "factored: every off-diagonal row T[.][j] shared by all children, two-valued (every "
-            f"table nem.py builds); or, with option exact_generic, a real-valued table with max|T|, max|U| <= "
-            f"{MAX_ABS_EXACT_GENERIC:g} and either the row T[.][j] shared by all children (per-effect log ratios; "
-            f"E <= {MAX_PARTS * NUMPY_BUFSIZE}, {MAX_PARTS} numpy buffers) or E <= {MAX_E_EXACT_GENERIC} (one "
+            f"table nem.py builds); or, with option exact_generic, a real-valued table with max|T| <= "
+            f"{MAX_ABS_T_EXACT_GENERIC:g}, max|U| <= {MAX_ABS_U_EXACT_GENERIC:g} and either the row T[.][j] shared by "
+            f"all children (per-effect log ratios; E <= {MAX_PARTS * NUMPY_BUFSIZE}, {MAX_PARTS} numpy buffers) or "
+            f"E <= {MAX_E_EXACT_GENERIC} (one "
             "numpy buffer)",
             "factored" if factored else f"generic, rows shared, E={E}", bool(factored) or parts is not None,
             f"ExactArithmeticWarning (strict=True: RuntimeError); the fast kernels -- a row-shared table with E > "
-            f"{MAX_PARTS * NUMPY_BUFSIZE} or max|T|, max|U| > {MAX_ABS_EXACT_GENERIC:g} (Engine.exact_status reads "
+            f"{MAX_PARTS * NUMPY_BUFSIZE}, max|T| > {MAX_ABS_T_EXACT_GENERIC:g} or max|U| > "
+            f"{MAX_ABS_U_EXACT_GENERIC:g} (Engine.exact_status reads "
             "the library's verdict on the staged values)", False)
     elif exact_generic:
         table_form = Limit(
             "table form", "factored: every off-diagonal row T[.][j] shared by all children, two-valued (every "
             f"table nem.py builds); or, with option exact_generic, any real-valued table with E <= "
-            f"{MAX_E_EXACT_GENERIC} (one numpy buffer) and max|T|, max|U| <= {MAX_ABS_EXACT_GENERIC:g}",
+            f"{MAX_E_EXACT_GENERIC} (one numpy buffer), max|T| <= {MAX_ABS_T_EXACT_GENERIC:g} and max|U| <= "
+            f"{MAX_ABS_U_EXACT_GENERIC:g}",
             "factored" if factored else f"generic, E={E}", bool(factored) or E <= MAX_E_EXACT_GENERIC,
             f"ExactArithmeticWarning (strict=True: RuntimeError); the fast kernels -- a generic table with E > "
-            f"{MAX_E_EXACT_GENERIC} or max|T|, max|U| > {MAX_ABS_EXACT_GENERIC:g} (Engine.exact_status reads the "
+            f"{MAX_E_EXACT_GENERIC}, max|T| > {MAX_ABS_T_EXACT_GENERIC:g} or max|U| > {MAX_ABS_U_EXACT_GENERIC:g} "
+            "(Engine.exact_status reads the "
             "library's verdict on the staged values)", False)
     else:
         table_form = Limit(
@@ -114,10 +126,11 @@ def exact_limits(S: int, E: int, factored: bool, cap: int = 0, host_blas: str | 
               False),
         table_form,
         Limit("E (effects)", f"np.sum of E terms in <= {MAX_PARTS} numpy buffers of {NUMPY_BUFSIZE} (E <= "
-              f"{MAX_PARTS * NUMPY_BUFSIZE}; each buffer summed pairwise in <= {MAX_LEAVES} leaf blocks, the "
-              "buffers in order) -- with numpy's default np.getbufsize()",
+              f"{MAX_PARTS * NUMPY_BUFSIZE}; each buffer summed pairwise in <= {MAX_LEAVES} leaf blocks -- every "
+              "buffer size but 441 in 7689 .. 8191, which split into 65 -- the buffers in order) -- with numpy's "
+              "default np.getbufsize()",
               f"E={E}: {leaves} leaves" + (f", {len(parts)} buffers" if parts and len(parts) > 1 else ""),
-              parts is not None,
+              e_covered,
               "ExactArithmeticWarning (strict=True: RuntimeError); the fast kernels"
               + ("" if E <= MAX_E_FAST_LOCAL_OPT else f" -- which take E <= {MAX_E_FAST_LOCAL_OPT}: the step fails"),
               False),

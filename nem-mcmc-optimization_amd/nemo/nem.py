@@ -81,8 +81,8 @@ class TableModel:
     place of a ``NEM``: it has the attributes they read (``num_s``, ``num_e``,
     ``U``, ``get_score_tables``) and no knockdown matrix, so its engine is
     staged from the tables (``Engine.for_model``, option ``exact_generic``:
-    the reference's bits for max|T|, max|U| <= 700 and E <= 8192, or E <=
-    524288 for a model of log ratios).
+    the reference's bits for max|T| <= 670, max|U| <= 700 and E <= 8192, or E
+    <= 524288 for a model of log ratios).
 
     A sampler built on a ``TableModel`` without an ``engine=`` always takes
     that option.  A table with its own rows per child then runs the exact

@@ -33,12 +33,23 @@ static double pairwise_sum(const double* a, long n) {
   return pairwise_sum(a, n2) + pairwise_sum(a + n2, n - n2);
 }
 
+// np.sum of a contiguous array: numpy hands the reduction its buffer-sized
+// chunks (np.getbufsize() = 8192 terms) in order, each summed pairwise and
+// added to the running result -- one pairwise recursion only up to 8192
+static double np_sum(const double* a, long n) {
+#pragma clang fp contract(off)
+  constexpr long kBuf = 8192;
+  double res = pairwise_sum(a, n < kBuf ? n : kBuf);
+  for (long off = kBuf; off < n; off += kBuf) res = res + pairwise_sum(a + off, n - off < kBuf ? n - off : kBuf);
+  return res;
+}
+
 // local_ll_sum_penalized (nem_order_mcmc.py:18-23) as numpy evaluates it
 static double objective(const double* c, int E, double anc, double x, double* buf) {
 #pragma clang fp contract(off)
   const double ex = refmath::expit(x);
   for (int e = 0; e < E; ++e) buf[e] = refmath::svml_log(c[e] * ex + 1.0);
-  const double temp1 = -pairwise_sum(buf, E);
+  const double temp1 = -np_sum(buf, E);
   const double temp2 = __builtin_fabs(ex - anc);
   return (temp1 + temp2) + ex * (1.0 - ex);
 }

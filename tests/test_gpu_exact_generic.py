@@ -301,7 +301,8 @@ def test_wide_table_fast_scores_equal_oracle(amax):
     s, e = 12, 100
     u, t = _wide_tables(amax)
     eng = _engine(u, t)
-    covered = amax <= 700.0
+    from nemo import limits
+    covered = amax <= limits.MAX_ABS_T_EXACT_GENERIC
     assert eng.get_option("exact_ok") == (1 if covered else 0)
     rng = np.random.default_rng(2)
     perms = [np.arange(s), np.arange(s)[::-1].copy(), rng.permutation(s)]
@@ -377,11 +378,19 @@ def test_generic_gates():
     eng.close()
     u, t = generic_tables("own", 4, 100, 7)
     t = t.copy()
-    t[1, 2, 5] = 701.0                      # max|T| = 701
+    from nemo import limits
+    tmax = limits.MAX_ABS_T_EXACT_GENERIC
+    assert tmax == 670.0
+    for v in (701.0, 700.0, -700.0, 671.0, np.nextafter(tmax, np.inf)):
+        t[1, 2, 5] = v                      # max|T| past the bound: a flushed order weight could change c
+        eng = _engine(u, t)
+        _warns_uncovered(eng, u, t)
+        eng.close()
+    t[1, 2, 5] = -tmax
     eng = _engine(u, t)
-    _warns_uncovered(eng, u, t)
+    assert eng.get_option("exact_ok") == 1
     eng.close()
-    t[1, 2, 5] = 700.0                      # ... and 700 is covered
+    t[1, 2, 5] = tmax                       # ... and 670 is covered
     eng = _engine(u, t)
     assert eng.get_option("exact_ok") == 1 and eng.exact_status() == (True, "")
     with pytest.raises(_lib.NemoError) as ei:   # staged: the option is fixed

@@ -262,9 +262,16 @@ def test_tables_outside_the_new_bounds_stay_uncovered():
     eng = Engine.from_log_ratios(r)          # max|R| = 701
     assert eng.get_option("exact_shared") == 1 and eng.get_option("exact_ok") == 0
     ok, why = eng.exact_status()
-    assert not ok and why.startswith("table form") and "700" in why
+    assert not ok and why.startswith("table form") and "700" in why and "670" in why
     eng.close()
-    r[2, 5] = 700.0                          # ... and 700 is covered
+    from nemo import limits
+    for v in (700.0, 671.0):                 # past max|T| <= 670: a flushed order weight could change c
+        r[2, 5] = v
+        eng = Engine.from_log_ratios(r)
+        assert eng.get_option("exact_shared") == 1 and eng.get_option("exact_ok") == 0
+        assert not eng.exact_status()[0]
+        eng.close()
+    r[2, 5] = limits.MAX_ABS_T_EXACT_GENERIC  # ... and 670 is covered
     eng = Engine.from_log_ratios(r)
     assert eng.get_option("exact_ok") == 1 and eng.exact_status() == (True, "")
     eng.close()

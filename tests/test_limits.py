@@ -64,6 +64,42 @@ def test_device_ancestor_limit_keeps_the_bits():
     assert _status(S=65)[0] and _status(host_blas="Haswell")[0]      # the step itself keeps the bits
 
 
+def test_buffer_sizes_of_65_leaves_are_not_covered():
+    """numpy's recursion splits 441 sizes in 7689 .. 8191 into 65 leaf blocks
+    (8191 among them), one more than the wave plan's lanes hold: the staging
+    builds no plan there (exact_ok 0, tests/test_gpu_exact_edges.py), and the
+    E row says so -- for E itself and for a last buffer of such a size."""
+    bad = [n for n in range(1, 8193) if limits.pairwise_leaves(n) > limits.MAX_LEAVES]
+    assert len(bad) == 441 and bad[0] == 7689 and bad[-1] == 8191
+    assert max(limits.pairwise_leaves(n) for n in range(1, 8193)) == 65
+    for e in (7688, 8184, 8192, 8193, 8192 + 7688, 3 * 8192):
+        assert _status(E=e) == (True, ""), e
+    for e in (7689, 8191, 8192 + 8191, 5 * 8192 + 7689):
+        ok, why = _status(E=e)
+        assert not ok and why.startswith("E (effects)") and "65" in why, e
+
+
+def test_exact_generic_bounds_are_the_librarys():
+    """The bounds of option exact_generic are one pair of constants: the
+    library's (include/nemo.h, read by stage_exact_generic) and nemo.limits'
+    hold the same values, and 670 is the derived one: a flushed order weight
+    (<= e^-707.70) gives |c| <= e^(|T| - 707.70), below 2^-54 at 670 and not at
+    671."""
+    import math
+    import os
+    import re
+    from conftest import REPO
+    text = open(os.path.join(REPO, "include", "nemo.h")).read()
+    t = float(re.search(r"#define NEMO_EXACT_GENERIC_MAX_ABS_T\s+([0-9.]+)", text).group(1))
+    u = float(re.search(r"#define NEMO_EXACT_GENERIC_MAX_ABS_U\s+([0-9.]+)", text).group(1))
+    assert (t, u) == (limits.MAX_ABS_T_EXACT_GENERIC, limits.MAX_ABS_U_EXACT_GENERIC) == (670.0, 700.0)
+    assert math.exp(t - 707.70) < 2.0 ** -54 < math.exp(t + 1.0 - 707.70)
+    abi = open(os.path.join(REPO, "nem-mcmc-optimization_amd", "csrc", "nemo_abi.cpp")).read()
+    assert "amax <= NEMO_EXACT_GENERIC_MAX_ABS_T" in abi and "<= NEMO_EXACT_GENERIC_MAX_ABS_U" in abi
+    row = {r.name: r for r in limits.exact_limits(9, 300, False, exact_generic=True)}["table form"]
+    assert "max|T| <= 670" in row.bound and "max|U| <= 700" in row.bound
+
+
 def test_table_renders_every_row():
     md = limits.limits_table_markdown(limits.exact_limits(64, 2000, True))
     assert md.count("\n") == 1 + len(limits.exact_limits(64, 2000, True))
