@@ -155,6 +155,42 @@ int nemo_score_grad(nemo_ctx* ctx, int batch, const int32_t* pos, const double* 
 int nemo_score_grad_dev(nemo_ctx* ctx, int batch, const int32_t* d_pos, const double* d_w01, int cap,
                         double* d_ll, double* d_grad, void* stream);
 
+/* ---- exact score change of every single-weight move -----------------------
+ * What a greedy search over the DAG of a fixed order (the nem R package's
+ * nem.greedy), an edge-Gibbs conditional or a finite-difference check of the
+ * gradient asks: what does the score become if this ONE weight changes?  With
+ * f_ij(e) = 1 - w_ij + w_ij v, v = exp(T[i][j][e]), and ow = exp(cell - cs),
+ * replacing w_ij by w'_ij moves only row i of the cells, so in closed form,
+ * with no differencing of two scores,
+ *   ll(w with w_ij := w'_ij) - ll(w) = sum_e log1p(ow[i][e] kappa_ij(e)),
+ *   kappa_ij(e) = (w'_ij - w_ij) (v - 1) / f_ij(e)
+ * -- exact to fp64 rounding however small the move's effect; nemo_score_grad
+ * is this sum's first-order term.  No reference counterpart runs, so "exact" /
+ * "exact_dev" / "fact_kernel" do not route this call.
+ *   w_alt    [batch][S][S]  the value each permissible pair would take; read
+ *                           only at the permissible pairs, exactly where w01 is
+ *   ll_out   [batch]        as nemo_score_grad
+ *   dll_out  [batch][S][S]  the sum above at the permissible pairs (each entry
+ *                           is the change of that one move alone); exactly
+ *                           +0.0 elsewhere (every entry is written), and
+ *                           exactly 0.0 where w_alt == w01
+ * cap as for nemo_score.  NEMO_F64 contexts only (NEMO_F32: NEMO_ERR_ARG); a
+ * wide generic table is served (no products of exp(T) are taken).  A factored
+ * model with S <= 64 runs one fused kernel between the factored prep and a
+ * finish (nemo_score_grad's MFMA forward, then one log1p per pair and effect
+ * from the order weights in the LDS), everything else two passes: the forward
+ * with order weights into the context's scratch, then a reduction (option
+ * "moves_path").  Every sum has a fixed order that depends on the staged
+ * model alone: an evaluation's bits depend neither on the batch, nor on its
+ * slot in it, nor on the run.  The host entry wants w_alt finite within [0, 1]
+ * at the permissible pairs (else NEMO_ERR_ARG; it does not look elsewhere).
+ * _dev: enqueue only; after nemo_reserve(max_batch, .) with batch <=
+ * max_batch it neither allocates nor synchronises (else NEMO_ERR_STATE). */
+int nemo_score_moves(nemo_ctx* ctx, int batch, const int32_t* pos, const double* w01, const double* w_alt,
+                     int cap, double* ll_out, double* dll_out);
+int nemo_score_moves_dev(nemo_ctx* ctx, int batch, const int32_t* d_pos, const double* d_w01,
+                         const double* d_w_alt, int cap, double* d_ll, double* d_dll, void* stream);
+
 /* ---- the error rates as parameters: score and gradient in per-gene A_k, B_k --
  * The closing comment of nem.py ("shared probability between clusters for the
  * error rates, use that as a latent variable") names what the reference never
@@ -374,6 +410,11 @@ int nemo_real_sweep(nemo_ctx* ctx, int nprob, const int32_t* pos, const double* 
  *                two-pass path always (tests, A/B measurement)
  *   "grad_path_used" (get only) the path the last nemo_score_grad(_dev) ran:
  *                1 two-pass, 2 fused; 0 before any call
+ *   "moves_path" 0 (default) auto: nemo_score_moves runs the fused kernel for a
+ *                factored model with S <= 64, else the two-pass path; 1 = the
+ *                two-pass path always (tests, A/B measurement)
+ *   "moves_path_used" (get only) the path the last nemo_score_moves(_dev) ran:
+ *                1 two-pass, 2 fused; 0 before any call
  *   "factored"   (get only) 1 if the staged table is factorable
  *   "win"        (get only) 1 if the capped lookup-table kernel is staged
  *                (U - U[S] two-valued per row, partial sums in range)
@@ -491,7 +532,8 @@ int nemo_real_sweep(nemo_ctx* ctx, int nprob, const int32_t* pos, const double* 
  *                plan parts, 7 slot); 0 before any launch
  *   "timing_kernel" 0 (default): nemo_timing_enable / _read time the score
  *                kernels; 1: the exact local optima's kernel (bench.py);
- *                2: nemo_real_sweep's pair solves (tools/real_score_time.py)
+ *                2: nemo_real_sweep's pair solves (tools/real_score_time.py);
+ *                3: nemo_score_moves' kernels (tools/moves_bench.py)
  *   "anc_overlap" 1 (default): nemo_optimal_weights_w makes ancestor_x on a
  *                second stream beside eval #1 (same bits); 0 = in line */
 int nemo_set_option(nemo_ctx* ctx, const char* name, int value);

@@ -189,7 +189,7 @@ void nemo_ctx_destroy(nemo_ctx* ctx) {
                   c.d_xa,   c.d_xbits, c.d_pwpos, c.d_pwmeta, c.d_xtrace, c.d_xqueue,
                   c.d_xcost, c.d_xorder, c.d_xhist, c.d_xsbuf, c.d_xX, c.d_xl,
                   c.d_grad, c.d_gradM, c.d_gradll, c.d_Dw, c.d_nk, c.d_rexp, c.d_rdiag,
-                  c.d_rates, c.d_drates};
+                  c.d_rates, c.d_drates, c.d_walt, c.d_movep, c.d_movell};
   for (void* p : bufs)
     if (p) (void)hipFree(p);
   for (int k = 0; k < Ctx::kStepSlots; ++k) {
@@ -246,7 +246,11 @@ int nemo_reserve(nemo_ctx* ctx, int max_batch, int max_chains) {
         HIPCHK(dalloc(&c.d_rdiag, nb * np * sp));
         HIPCHK(dalloc(&c.d_rates, nb * 2 * S));
         HIPCHK(dalloc(&c.d_drates, nb * 2 * S));
+        // nemo_score_moves: the fused kernel's partial sums by pair slot
+        HIPCHK(dalloc(&c.d_movep, nb * np * nemo::moves_part_doubles((int)sp)));
+        HIPCHK(dalloc(&c.d_movell, nb * np));
       }
+      HIPCHK(dalloc(&c.d_walt, nb * S * S));  // ... and its host entry's alternative weights
     }
     c.cap_batch = nb;
     if (nemo::host::kFactKernels[c.fact_kernel].split) HIPCHK(nemo::i8img_reserve(c));
@@ -851,6 +855,25 @@ int nemo_score(nemo_ctx* ctx, int batch, const int32_t* pos, const double* w01, 
   return NEMO_OK;
 }
 
+// the first of the two passes of nemo_score_grad and nemo_score_moves: the
+// forward with order weights into the context's d_ow (the chunked fp64 kernel,
+// or the streaming one), ll into d_ll
+static int forward_ow(Ctx& c, bool fact, int batch, int cap, const int32_t* d_pos, const double* d_w01, double* d_ll,
+                      hipStream_t st) {
+  if (fact) {
+    const int fk = c.fact_kernel;
+    c.fact_kernel = 1;  // option fact_kernel does not route this call
+    const hipError_t e = nemo::launch_score_factored(c, batch, cap, d_pos, d_w01, d_ll, nullptr, nullptr, c.d_ow, st);
+    c.fact_kernel = fk;
+    HIPCHK(e);
+  } else {
+    HIPCHK(nemo::launch_prep(c, batch, cap, d_pos, d_w01, c.d_rows, c.d_sw, c.d_cnt, nullptr, st));
+    HIPCHK(nemo::launch_score(c, batch, c.d_rows, c.d_sw, c.d_cnt, d_ll, nullptr, nullptr, c.d_ow, st));
+  }
+  c.ow_chains = 0;  // d_ow no longer holds fused-step order weights
+  return NEMO_OK;
+}
+
 // ---- d ll / d w01 (nemo_grad.hip) ----
 int nemo_score_grad_dev(nemo_ctx* ctx, int batch, const int32_t* d_pos, const double* d_w01, int cap,
                         double* d_ll, double* d_grad, void* stream) {
@@ -872,19 +895,7 @@ int nemo_score_grad_dev(nemo_ctx* ctx, int batch, const int32_t* d_pos, const do
     c.grad_path_used = 2;
     return NEMO_OK;
   }
-  // two passes: the forward with order weights into the context's d_ow (the
-  // chunked fp64 kernel, or the streaming one), then the reduction
-  if (fact) {
-    const int fk = c.fact_kernel;
-    c.fact_kernel = 1;  // option fact_kernel does not route this call
-    const hipError_t e = nemo::launch_score_factored(c, batch, cap, d_pos, d_w01, d_ll, nullptr, nullptr, c.d_ow, st);
-    c.fact_kernel = fk;
-    HIPCHK(e);
-  } else {
-    HIPCHK(nemo::launch_prep(c, batch, cap, d_pos, d_w01, c.d_rows, c.d_sw, c.d_cnt, nullptr, st));
-    HIPCHK(nemo::launch_score(c, batch, c.d_rows, c.d_sw, c.d_cnt, d_ll, nullptr, nullptr, c.d_ow, st));
-  }
-  c.ow_chains = 0;  // d_ow no longer holds fused-step order weights
+  if ((rc = forward_ow(c, fact, batch, cap, d_pos, d_w01, d_ll, st))) return rc;
   HIPCHK(nemo::launch_grad_reduce(c, batch, cap, fact, d_pos, d_w01, c.d_ow, d_grad, st));
   c.grad_path_used = 1;
   return NEMO_OK;
@@ -909,6 +920,64 @@ int nemo_score_grad(nemo_ctx* ctx, int batch, const int32_t* pos, const double* 
   if ((rc = nemo_score_grad_dev(ctx, batch, c.d_pos, c.d_w01, cap, c.d_ll, c.d_grad, st))) return rc;
   HIPCHK(hipMemcpyAsync(ll_out, c.d_ll, batch * 8, hipMemcpyDeviceToHost, st));
   HIPCHK(hipMemcpyAsync(grad_out, c.d_grad, batch * S * S * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return NEMO_OK;
+}
+
+// ---- ll(w with w_ij := w_alt_ij) - ll(w) of every permissible pair (nemo_moves.hip) ----
+int nemo_score_moves_dev(nemo_ctx* ctx, int batch, const int32_t* d_pos, const double* d_w01, const double* d_w_alt,
+                         int cap, double* d_ll, double* d_dll, void* stream) {
+  int rc = check_ctx(ctx, true);
+  if (rc) return rc;
+  Ctx& c = ctx->c;
+  if (c.dtype != NEMO_F64)
+    return fail(NEMO_ERR_ARG, "nemo_score_moves: dtype f32 (NEMO_F32) context; the move scores are fp64 only (NEMO_F64)");
+  if (batch < 0 || cap < 0) return fail(NEMO_ERR_ARG, "batch=%d cap=%d", batch, cap);
+  if (batch == 0) return NEMO_OK;
+  if (batch > c.cap_batch) return fail(NEMO_ERR_STATE, "batch %d > reserved %d", batch, c.cap_batch);
+  if (!d_pos || !d_w01 || !d_w_alt || !d_ll || !d_dll) return fail(NEMO_ERR_ARG, "null device pointer");
+  if (c.score_path == 2 && !c.factored)
+    return fail(NEMO_ERR_STATE, "score_path=2 (factored) but the staged table is not factorable");
+  hipStream_t st = pick(ctx, stream);
+  const bool fact = use_factored(c);
+  if (fact && c.fspad <= 64 && c.moves_path != 1) {
+    if (!nemo::moves_ready(c)) return fail(NEMO_ERR_STATE, "nemo_score_moves: scratch not reserved");
+    HIPCHK(nemo::launch_score_moves_fused(c, batch, cap, d_pos, d_w01, d_w_alt, d_ll, d_dll, st));
+    c.moves_path_used = 2;
+    return NEMO_OK;
+  }
+  if ((rc = forward_ow(c, fact, batch, cap, d_pos, d_w01, d_ll, st))) return rc;
+  HIPCHK(nemo::launch_moves_reduce(c, batch, cap, fact, d_pos, d_w01, d_w_alt, c.d_ow, d_dll, st));
+  c.moves_path_used = 1;
+  return NEMO_OK;
+}
+
+int nemo_score_moves(nemo_ctx* ctx, int batch, const int32_t* pos, const double* w01, const double* w_alt, int cap,
+                     double* ll_out, double* dll_out) {
+  int rc = check_ctx(ctx, true);
+  if (rc) return rc;
+  Ctx& c = ctx->c;
+  if (c.dtype != NEMO_F64)
+    return fail(NEMO_ERR_ARG, "nemo_score_moves: dtype f32 (NEMO_F32) context; the move scores are fp64 only (NEMO_F64)");
+  if (batch < 0 || cap < 0) return fail(NEMO_ERR_ARG, "batch=%d cap=%d", batch, cap);
+  if (batch == 0) return NEMO_OK;
+  if (!pos || !w01 || !w_alt || !ll_out || !dll_out) return fail(NEMO_ERR_ARG, "null host pointer");
+  if ((rc = check_pos(pos, batch, c.S))) return rc;
+  if (const size_t bad = nemo::host::check_w_alt(pos, w_alt, batch, c.S, cap)) {
+    const size_t k = bad - 1, SS = (size_t)c.S * c.S;
+    return fail(NEMO_ERR_ARG, "nemo_score_moves: w_alt[%zu][%zu][%zu] = %g is not finite within [0, 1]", k / SS,
+                (k % SS) / c.S, k % c.S, w_alt[k]);
+  }
+  if ((rc = nemo_reserve(ctx, batch, 0))) return rc;
+  const size_t S = c.S;
+  hipStream_t st = c.stream;
+  HIPCHK(hipMemcpyAsync(c.d_pos, pos, batch * S * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(c.d_w01, w01, batch * S * S * 8, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(c.d_walt, w_alt, batch * S * S * 8, hipMemcpyHostToDevice, st));
+  // (d_grad: the host entries run one at a time and end synchronised)
+  if ((rc = nemo_score_moves_dev(ctx, batch, c.d_pos, c.d_w01, c.d_walt, cap, c.d_ll, c.d_grad, st))) return rc;
+  HIPCHK(hipMemcpyAsync(ll_out, c.d_ll, batch * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(dll_out, c.d_grad, batch * S * S * 8, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   return NEMO_OK;
 }
@@ -1835,8 +1904,10 @@ int nemo_set_option(nemo_ctx* ctx, const char* name, int value) {
     return NEMO_OK;
   }
   if (strcmp(name, "timing_kernel") == 0) {
-    if (value < 0 || value > 2)
-      return fail(NEMO_ERR_ARG, "timing_kernel %d (0 score kernels, 1 exact local optima, 2 real-score pair solves)", value);
+    if (value < 0 || value > 3)
+      return fail(NEMO_ERR_ARG,
+                  "timing_kernel %d (0 score kernels, 1 exact local optima, 2 real-score pair solves, 3 move scores)",
+                  value);
     ctx->c.timing_kernel = value;
     return NEMO_OK;
   }
@@ -1897,6 +1968,11 @@ int nemo_set_option(nemo_ctx* ctx, const char* name, int value) {
     ctx->c.grad_path = value;
     return NEMO_OK;
   }
+  if (strcmp(name, "moves_path") == 0) {
+    if (value < 0 || value > 1) return fail(NEMO_ERR_ARG, "moves_path=%d not in {0,1}", value);
+    ctx->c.moves_path = value;
+    return NEMO_OK;
+  }
   if (strcmp(name, "score_path") == 0) {
     if (value < 0 || value > 2) return fail(NEMO_ERR_ARG, "score_path=%d not in {0,1,2}", value);
     ctx->c.score_path = value;
@@ -1914,6 +1990,8 @@ int nemo_get_option(nemo_ctx* ctx, const char* name, int* value) {
   else if (strcmp(name, "score_path") == 0) *value = c.score_path;
   else if (strcmp(name, "grad_path") == 0) *value = c.grad_path;
   else if (strcmp(name, "grad_path_used") == 0) *value = c.grad_path_used;
+  else if (strcmp(name, "moves_path") == 0) *value = c.moves_path;
+  else if (strcmp(name, "moves_path_used") == 0) *value = c.moves_path_used;
   else if (strcmp(name, "factored") == 0) *value = c.factored ? 1 : 0;
   else if (strcmp(name, "fact_kernel") == 0) *value = c.fact_kernel;
   else if (strcmp(name, "i8o") == 0) *value = c.i8o_ok ? (c.i8o_diag ? 2 : 1) : 0;

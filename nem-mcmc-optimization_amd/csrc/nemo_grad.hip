@@ -37,6 +37,7 @@
 // The same kernel with RATES set serves nemo_score_rates: the score at each
 // evaluation's own per-gene error rates with its derivatives in them, from M,
 // R and the diagonal M_kk (rates_finish_kernel below).
+#include "nemo_grad_fwd.h"
 #include "nemo_internal.h"
 
 #include <math.h>
@@ -44,36 +45,6 @@
 namespace nemo {
 
 namespace {
-
-using f64x4 = __attribute__((ext_vector_type(4))) double;
-
-__device__ __forceinline__ double gwave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, kWave);
-  return v;
-}
-
-// max over each 16-lane row, in every lane of the row (rowsum16's moves)
-__device__ __forceinline__ double rowmax16(double v) {
-  v = fmax(v, dpp_d<0xB1>(v));
-  v = fmax(v, dpp_d<0x4E>(v));
-  v = fmax(v, dpp_d<0x141>(v));
-  v = fmax(v, dpp_d<0x140>(v));
-  return v;
-}
-
-__device__ __forceinline__ int gxcd_work_index(int L, int N, int remap) {
-  if (!remap) return L;
-  const int x = L & 7, k = L >> 3;
-  const int q = N >> 3, r = N & 7;
-  return x * q + (x < r ? x : r) + k;
-}
-
-// f' of one value v = e^t of a pair's table row at weight w
-__device__ __forceinline__ double fprime(double w, double v) { return (v - 1.0) / fma(w, v, 1.0 - w); }
-
-// position of a node in the order, clamped as the prep kernels clamp it
-__device__ __forceinline__ int clamp_pos(int p, int S) { return p < 0 ? 0 : (p >= S ? S - 1 : p); }
 
 // ---------------------------------------------------------------------------
 // fused: grid = batch * nparts (evaluation-major, XCD remap), block =
@@ -97,12 +68,12 @@ __global__ __launch_bounds__(kGradWaves* kWave) void score_grad_fused_kernel(
     int S, int E, int ntiles, int nparts, const double* __restrict__ Dp, const int32_t* __restrict__ permo,
     const uint64_t* __restrict__ D1w, int nwords, const double* __restrict__ U, double* __restrict__ Mpart,
     double* __restrict__ llpart, int remap, const double* __restrict__ rates, double* __restrict__ Dpart) {
-  constexpr int SPAD = NR * 16;
-  constexpr int LDA = SPAD + 2;  // == 2 mod 32: conflict-free b64 Delta fragments
-  constexpr int NS = SPAD / 4;
+  using L = GradFwdLds<NR>;
+  constexpr int SPAD = L::SPAD;
+  constexpr int LDA = L::LDA;
   constexpr int NT = NR * (NR + 1) / 2;
-  constexpr int TPB = kGradWaves * kGradTilesPerWave;
-  constexpr int NWB = TPB * 16 / 64;  // D1 words per parent row of a part (parts start on a word)
+  constexpr int TPB = L::TPB;
+  constexpr int NWB = L::NWB;
   static_assert(SPAD * LDA >= NT * 256, "the wave reduction reuses Delta's LDS");
   extern __shared__ __attribute__((aligned(16))) double lds[];
   double* etab = lds;                              // [256] 2^(j/256)
@@ -125,19 +96,7 @@ __global__ __launch_bounds__(kGradWaves* kWave) void score_grad_fused_kernel(
   const int col = lane & 15, rg = lane >> 4;
 
   const int32_t* pm = permo + (size_t)b * SPAD;
-  if (tid < 256) etab[tid] = exp2((double)tid * (1.0 / 256.0));
-  fill_log_table(ltab, tid, blockDim.x);
-  for (int k = tid; k < SPAD * NWB; k += blockDim.x) {
-    const int u = k / SPAD, p = k - u * SPAD;
-    const int node = pm[p];
-    const int wi = w_lo + u;
-    words[k] = (node < S && wi < nwords) ? D1w[(size_t)node * nwords + wi] : 0ull;
-  }
-  const double* Db = Dp + (size_t)b * SPAD * SPAD;
-  for (int k = tid; k < SPAD * SPAD; k += blockDim.x) {
-    const int row = k / SPAD, kk = k - row * SPAD;
-    if (kk <= (row | 15)) A[row * LDA + kk] = Db[k];
-  }
+  grad_fwd_stage<NR>(lds, S, nwords, w_lo, pm, Dp + (size_t)b * SPAD * SPAD, D1w);
   // rows of U of this lane's NR child positions (S = the null row: padding)
   // (element offsets: (S + 1) E < 2^31 for S <= 64 at every E the staging takes)
   uint32_t urow[NR];
@@ -170,12 +129,7 @@ __global__ __launch_bounds__(kGradWaves* kWave) void score_grad_fused_kernel(
     const int bit0 = (t * 16) & 63;
     const uint64_t* wt = words + (size_t)uidx * SPAD;
     if constexpr (!RATES) {
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int ec = min(t * 16 + 4 * g + rg, E - 1);
-#pragma unroll
-        for (int r = 0; r < NR; ++r) acc[r][g] = U[urow[r] + ec];
-      }
+      grad_fwd_uinit<NR>(acc, t, E, U, urow, rg);
     } else {
 #pragma unroll
       for (int r = 0; r < NR; ++r) {
@@ -185,19 +139,7 @@ __global__ __launch_bounds__(kGradWaves* kWave) void score_grad_fused_kernel(
         for (int g = 0; g < 4; ++g) acc[r][g] = ((ob >> (4 * g)) & 1u) ? o1 : o0;
       }
     }
-#pragma unroll
-    for (int s = 0; s < NS; ++s) {
-      const uint32_t bv = (uint32_t)((wt[4 * s + rg] >> (bit0 + col)) & 1ull);
-#pragma unroll
-      for (int r = 0; r < NR; ++r) {
-        if (4 * s <= 16 * r + 12) {
-          // column 16 r + 15 of Delta's row block r holds G: the bit is 1 there
-          const uint32_t bb = (4 * s == 16 * r + 12) ? (bv | diag) : bv;
-          const double d = A[(16 * r + col) * LDA + 4 * s + rg];
-          acc[r] = __builtin_amdgcn_mfma_f64_16x16x4f64((double)bb, d, acc[r], 0, 0, 0);
-        }
-      }
-    }
+    grad_fwd_mfma<NR>(acc, wt, bit0, A, col, rg, diag);
     // the D1 bits of the second contraction's A fragments: bit 4 g of pb[rp] is
     // D1[p = 16 rp + col][effect 4 g + rg]
     uint32_t pb[NR];
@@ -211,6 +153,8 @@ __global__ __launch_bounds__(kGradWaves* kWave) void score_grad_fused_kernel(
       const bool valid = e < E;
       double unull = 0.0;
       if constexpr (!RATES) unull = U[(size_t)S * E + (valid ? e : E - 1)];
+      // (grad_fwd_lse's text, kept in line: through the call this kernel's NR = 4
+      // instance goes from 254 VGPRs to 256 with scratch spills)
       double m = acc[0][g];
 #pragma unroll
       for (int r = 1; r < NR; ++r) m = fmax(m, acc[r][g]);

@@ -46,6 +46,27 @@ inline int first_bad_pos_row(const int32_t* pos, int batch, int S) {
   return -1;
 }
 
+// nemo_score_moves' argument check: w_alt [batch][S][S] must be finite within
+// [0, 1] at the permissible pairs (pos[j] < pos[i], and pos[i] - pos[j] <= cap
+// when 0 < cap < S - 1) and is not looked at elsewhere (NaN is allowed there).
+// Returns 0, or 1 + the flat index of the first offending entry.  pos has
+// passed first_bad_pos_row.
+inline size_t check_w_alt(const int32_t* pos, const double* w_alt, int batch, int S, int cap) {
+  if (cap >= S - 1) cap = 0;
+  for (int b = 0; b < batch; ++b) {
+    const int32_t* pb = pos + (size_t)b * S;
+    for (int i = 0; i < S; ++i)
+      for (int j = 0; j < S; ++j) {
+        const int d = pb[i] - pb[j];
+        if (d <= 0 || (cap > 0 && d > cap)) continue;
+        const size_t k = ((size_t)b * S + i) * S + j;
+        const double v = w_alt[k];
+        if (!(v >= 0.0 && v <= 1.0)) return k + 1;  // (NaN fails both comparisons)
+      }
+  }
+  return 0;
+}
+
 // ---------------------------------------------------------------------------
 // Staging validation: the factored form of a score table
 // ---------------------------------------------------------------------------

@@ -121,6 +121,15 @@ struct Ctx {
   double* d_gradM = nullptr;       // [cap][grad_parts][grad_part_doubles] the fused kernel's partial M tiles
   double* d_gradll = nullptr;      // [cap][grad_parts] its partial ll
 
+  // exact score change of every single-weight move (nemo_moves.hip): option
+  // "moves_path" 0 auto (the fused kernel for a factored model with S <= 64,
+  // else the two-pass path), 1 = always two-pass; moves_path_used: the last call's
+  int moves_path = 0;
+  int moves_path_used = 0;
+  double* d_walt = nullptr;        // [cap][S][S] the host entry's alternative weights
+  double* d_movep = nullptr;       // [cap][grad_parts][moves_part_doubles] the fused kernel's partial sums by pair slot
+  double* d_movell = nullptr;      // [cap][grad_parts] its partial ll
+
   // score and gradient in per-gene error rates (nemo_score_rates): what
   // nemo_stage_knockdown keeps of D itself.  D's own words, not a flip flag per
   // row over d_D1w: D1 is "not the row's first value" and a constant row stages
@@ -260,8 +269,8 @@ struct Ctx {
   int step_graph_next = 0;
 
   // timing of the score kernel (timing_kernel 0) or of the exact local
-  // optima's kernel (1) or of the real-score pair solves (2; option
-  // "timing_kernel")
+  // optima's kernel (1) or of the real-score pair solves (2) or of the
+  // move-score kernels (3; option "timing_kernel")
   bool timing = false;
   int timing_kernel = 0;
   std::vector<hipEvent_t> ev_pool;
@@ -436,6 +445,28 @@ __device__ __forceinline__ double log_fast(double x, const double2* __restrict__
   p *= r;
   const double kd = (double)k;
   return fma(kd, kLn2Hi, tj.y) + fma(kd, kLn2Lo, p);
+}
+
+// log(1 + x) for finite x >= -1.  Below 2^-8 in magnitude the series x P(x) --
+// log_fast's own degree-6 polynomial with r = x, truncation x^6 / 7 < 2.3 * 2^-52
+// relative -- so the result is RELATIVELY accurate (a few ulp of itself) however
+// small x is; from there on log_fast(1 + x), whose error of ~1 ulp of
+// max(|log|, 0.5) is absolute.  Both are computed and one is selected: no
+// divergent branch.  The callers' x is ow kappa: 1 + x =
+// (1 - ow) + ow f(w') / f(w) is a convex combination of 1 and a ratio of two
+// factors 1 - w + w e^T, each positive for a finite table, with ow = exp(cell -
+// cs) in [0, 1] -- positive, as log_fast requires.  In fp64 the sum can still
+// round to 0 (ow = 1 and e^T < 2^-53: the true value needs 1 - ow, which ow no
+// longer holds); it then stands for a value in (0, 2^-54], and 2^-54 is taken.
+__device__ __forceinline__ double log1p_fast(double x, const double2* __restrict__ ltab) {
+  double p = fma(x, -1.0 / 6.0, 0.2);
+  p = fma(x, p, -0.25);
+  p = fma(x, p, 1.0 / 3.0);
+  p = fma(x, p, -0.5);
+  p = fma(x, p, 1.0);
+  p *= x;
+  const double big = log_fast(fmax(1.0 + x, 0x1p-54), ltab);
+  return fabs(x) < 0x1p-8 ? p : big;
 }
 
 // exp(x) for x <= ~0 in fp64 from a 64-entry table of 2^(j/64) and a
@@ -695,6 +726,26 @@ hipError_t launch_score_rates(Ctx& c, int batch, int cap, const int32_t* d_pos, 
 // (factored) or the staged exp(T) rows (generic, fp64)
 hipError_t launch_grad_reduce(Ctx& c, int batch, int cap, bool factored, const int32_t* d_pos,
                               const double* d_w01, const double* d_ow, double* d_grad, hipStream_t st);
+// ---- exact score change of every single-weight move (nemo_moves.hip) ----
+// dll[b][i][j] = ll(w01 with w_ij := w_alt_ij) - ll(w01) = sum_e log1p(ow[i][e]
+// kappa_ij(e)), kappa = (w' - w) (v - 1) / (1 - w + w v), at the permissible
+// pairs and +0.0 elsewhere.  The fused kernel gives pair (q, p), p < q in order
+// positions, the slot q (q - 1) / 2 + p -- a function of the padded S alone --
+// and leaves one partial sum per slot and part of E (grad_parts)
+constexpr int kMovesRoundTiles = 2;  // 16-effect tiles per round of the fused kernel's second half
+inline size_t moves_part_doubles(int spad) {
+  const size_t nthreads = (size_t)kGradWaves * kWave, npair = (size_t)spad * (spad - 1) / 2;
+  return (npair + nthreads - 1) / nthreads * nthreads;
+}
+inline bool moves_ready(const Ctx& c) { return c.d_movep && c.d_movell; }
+// prep_factored_kernel, the fused kernel and its finish (factored model, S <=
+// 64): ll [batch], dll [batch][S][S] (every entry written)
+hipError_t launch_score_moves_fused(Ctx& c, int batch, int cap, const int32_t* d_pos, const double* d_w01,
+                                    const double* d_walt, double* d_ll, double* d_dll, hipStream_t st);
+// the two-pass path's second pass over the order weights d_ow [batch][S+1][E]
+hipError_t launch_moves_reduce(Ctx& c, int batch, int cap, bool factored, const int32_t* d_pos,
+                               const double* d_w01, const double* d_walt, const double* d_ow, double* d_dll,
+                               hipStream_t st);
 // the fused step's prep in ONE launch: prep_kernel's parent and pair lists
 // with the info rows preset to -1, and prep_factored_kernel's Delta / G / perm
 hipError_t launch_step_prep(Ctx& c, int batch, int cap, const int32_t* d_pos, const double* d_w01,

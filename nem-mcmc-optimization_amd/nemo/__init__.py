@@ -9,7 +9,8 @@ of ``include/nemo.h`` (``libnemo.so``, loaded with ctypes).
 from . import generator, utils
 from .nem import NEM, TableModel
 
-__all__ = ["NEM", "TableModel", "generator", "utils", "Engine", "NEMOrderMCMC", "ExactArithmeticWarning"]
+__all__ = ["NEM", "TableModel", "generator", "utils", "Engine", "NEMOrderMCMC", "ExactArithmeticWarning",
+           "GreedyMethod", "greedy_flips"]
 
 
 def __getattr__(name):
@@ -23,4 +24,7 @@ def __getattr__(name):
     if name == "NEMOrderMCMC":
         from .nem_order_mcmc import NEMOrderMCMC
         return NEMOrderMCMC
+    if name in ("GreedyMethod", "greedy_flips"):
+        from . import methods
+        return getattr(methods, name)
     raise AttributeError(name)

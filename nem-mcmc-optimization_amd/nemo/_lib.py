@@ -46,6 +46,8 @@ SIGNATURES = [
     ("nemo_score_dev", C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     ("nemo_score_grad", C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp]),  # addr()
     ("nemo_score_grad_dev", C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp]),
+    ("nemo_score_moves", C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp]),  # addr()
+    ("nemo_score_moves_dev", C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp]),
     ("nemo_score_rates", C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp]),  # addr()
     ("nemo_score_rates_dev", C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp]),
     ("nemo_score_group_dev", C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp, _vp]),

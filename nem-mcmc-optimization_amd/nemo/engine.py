@@ -211,6 +211,29 @@ class Engine:
         the batch first)."""
         check(_lib.load().nemo_score_grad_dev(self._ctx, int(batch), d_pos, d_w01, int(cap), d_ll, d_grad, stream))
 
+    # -- the exact score change of every single-weight move ---------------------
+    def score_moves(self, pos, w01, w_alt, cap: int = 0):
+        """Order scores and the exact change of each under every single-weight
+        move: (ll (B,), dll (B, S, S)), dll[b, i, j] = ll[b] with w01[b, i, j]
+        replaced by w_alt[b, i, j] alone, minus ll[b], at the permissible pairs
+        and exactly 0 elsewhere (fp64 engines only).  ``w_alt`` is read only at
+        the permissible pairs and must lie in [0, 1] there."""
+        pos = i32(np.atleast_2d(pos))
+        b = pos.shape[0]
+        w01 = f64(w01).reshape(b, self.S, self.S)
+        w_alt = f64(w_alt).reshape(b, self.S, self.S)
+        ll = np.empty(b)
+        dll = np.empty((b, self.S, self.S))
+        a = _lib.addr
+        check(_lib.load().nemo_score_moves(self._ctx, b, a(pos), a(w01), a(w_alt), int(cap), a(ll), a(dll)))
+        return ll, dll
+
+    def score_moves_dev(self, batch, d_pos, d_w01, d_w_alt, d_ll, d_dll, cap=0, stream=None):
+        """Enqueue ``score_moves`` on device pointers (no sync; ``reserve``
+        the batch first)."""
+        check(_lib.load().nemo_score_moves_dev(self._ctx, int(batch), d_pos, d_w01, d_w_alt, int(cap), d_ll, d_dll,
+                                               stream))
+
     # -- the error rates as parameters ------------------------------------------
     def score_rates(self, pos, w01, A, B, cap: int = 0, want_grad_w: bool = True):
         """Order scores at per-gene error rates, with their derivatives, on an

@@ -219,4 +219,67 @@ class JointMethod(_Base):
         return weights.T, real_ll
 
 
-__all__ = ["InverseMethod", "Method", "JointMethod", "INVERSE_BOUNDS", "GAMMA_BOUNDS"]
+def greedy_flips(engine, pos, weights, cap=0, max_iter=None, min_gain=1e-9, ll_trace=None):
+    """Greedy search over the DAGs of fixed orders by single-edge flips (the
+    nem R package's ``nem.greedy`` within an order), B problems at once.
+
+    ``pos`` (B, S) order positions, ``weights`` (B, S, S) with entries in {0, 1}.
+    Every iteration is ONE ``engine.score_moves`` call over all B problems with
+    ``w_alt = 1 - w``: the exact score change of every single flip.  Each problem
+    applies its best flip if that gains more than ``min_gain`` (ties: the lowest
+    (i, j)), else it is finished; the loop ends when every problem is finished or
+    after ``max_iter`` iterations (default S * S).  -> (weights (B, S, S), ll
+    (B,), n_flips (B,)); ll is that of a final ``score_moves`` call on the
+    returned weights, not a running sum.  ``ll_trace``: a list that receives the
+    (B,) ll of every call, the final one included."""
+    pos = np.ascontiguousarray(np.atleast_2d(pos), dtype=np.int32)
+    b, s = pos.shape
+    w = np.array(weights, dtype=np.float64).reshape(b, s, s)
+    if not np.isin(w, (0.0, 1.0)).all():
+        raise ValueError("greedy_flips: weights must be 0 or 1")
+    ok = pos[:, :, None] > pos[:, None, :]
+    if 0 < cap < s - 1:
+        ok &= pos[:, :, None] - pos[:, None, :] <= cap
+    ok = ok.reshape(b, s * s)
+    max_iter = s * s if max_iter is None else int(max_iter)
+    n_flips = np.zeros(b, dtype=np.int64)
+    active = np.ones(b, dtype=bool)
+    rows = np.arange(b)
+    it = 0
+    while True:
+        ll, dll = engine.score_moves(pos, w, 1.0 - w, cap=cap)
+        if ll_trace is not None:
+            ll_trace.append(np.array(ll))
+        if it >= max_iter:
+            return w, np.array(ll), n_flips
+        gain = np.where(ok, np.asarray(dll).reshape(b, s * s), -np.inf)
+        best = gain.argmax(axis=1)          # the first maximum: the lowest (i, j)
+        active &= gain[rows, best] > min_gain
+        if not active.any():                # nothing flips: this call's ll is the final one
+            return w, np.array(ll), n_flips
+        flat = w.reshape(b, s * s)
+        flat[rows[active], best[active]] = 1.0 - flat[rows[active], best[active]]
+        n_flips += active
+        it += 1
+
+
+class GreedyMethod(_Base):
+    """Greedy single-edge search over the DAGs of one fixed order, every
+    iteration one ``nemo_score_moves`` call (``greedy_flips``).  There is no
+    reference counterpart in methods.py; the constructor, ``ll_list`` and
+    ``optimize``'s return follow ``Method``."""
+
+    def optimize(self, start=None, max_iter=None):
+        """-> (weights.T, ll).  ``start``: a 0/1 weight matrix (default all
+        zeros; entries off the permissible pairs are dropped).  ``ll_list``
+        holds the ll at the start of each iteration, then the final one."""
+        w = np.zeros((self.num_s, self.num_s)) if start is None else np.asarray(start, dtype=np.float64) * self.mask
+        trace = []
+        weights, ll, n = greedy_flips(self.engine, self._pos[None, :], w[None], max_iter=max_iter, ll_trace=trace)
+        self.ll_list = [float(v[0]) for v in trace]
+        self.n_flips = int(n[0])
+        print(f"Greedy LL: {float(ll[0])} after {self.n_flips} flips")
+        return (1 * (weights[0] > 0.5)).T, float(ll[0])
+
+
+__all__ = ["InverseMethod", "Method", "JointMethod", "GreedyMethod", "greedy_flips", "INVERSE_BOUNDS", "GAMMA_BOUNDS"]
