@@ -81,6 +81,11 @@ int nemo_device_count(int* count);
 #define NEMO_EXACT_GENERIC_MAX_ABS_T 670.0
 #define NEMO_EXACT_GENERIC_MAX_ABS_U 700.0
 
+/* nemo_edge_sweep: the most effects one evaluation's block holds in its
+ * registers, 16 per thread of 1024 (nemo.limits.MAX_E_EDGE_SWEEP holds the
+ * same value); a model with more is refused with NEMO_ERR_ARG */
+#define NEMO_EDGE_SWEEP_MAX_E 16384
+
 /* ---- context lifetime (replaces NEMOrderMCMC.__init__'s table setup,
  *      nem_order_mcmc.py:40-46) ------------------------------------------
  * num_s in [2, 256] (a model of one S-gene has no parent pair: num_s = 1 is
@@ -190,6 +195,56 @@ int nemo_score_moves(nemo_ctx* ctx, int batch, const int32_t* pos, const double*
                      int cap, double* ll_out, double* dll_out);
 int nemo_score_moves_dev(nemo_ctx* ctx, int batch, const int32_t* d_pos, const double* d_w01,
                          const double* d_w_alt, int cap, double* d_ll, double* d_dll, void* stream);
+
+/* ---- one sweep over the single-weight moves, each taken or not in turn -----
+ * nemo_score_moves scores every move at ONE state; once a move is taken every
+ * other score is stale.  This call walks the permissible pairs in sequence and
+ * keeps the state exact across the moves it takes: a Gibbs sweep over the
+ * edges of a fixed order, or one round of coordinate ascent, in one launch.
+ * With x_e = ow[i][e] kappa_ij(e) and t_e = log1p(x_e), taking move (i, j) is
+ *   cs[e] += t_e,  ow[i][e] *= (1 + kappa_ij(e)) / (1 + x_e),
+ *   ow[k][e] /= 1 + x_e  (k != i),
+ * so one number per effect, c[e] = the change of cs[e] so far, carries the
+ * sweep: child i's row is ow0[i][e] exp(-c[e]) when its turn comes (ow0: the
+ * forward's order weights) and the swept weights score ll0 + sum_e c[e].
+ *   visit order  children by order position q = 1 .. S-1 ascending, within a
+ *                child its permissible parents by order position ascending;
+ *                each pair once
+ *   gain         sum_e log1p(ow_cur[i][e] kappa_ij(e)) at the current state,
+ *                kappa as in nemo_score_moves from w01[i][j] and w_alt[i][j];
+ *                exactly +0.0 where w_alt == w01
+ *   decision     taken iff gain > thr[i][j], strictly: +inf never, -inf always
+ *   thr      [batch][S][S]  read only at the permissible pairs
+ *   w_out    [batch][S][S]  w_alt[i][j] where the move was taken, else
+ *                           w01[i][j]; alt_out the other one (bits copied, no
+ *                           arithmetic): a call on (w_out, alt_out) proposes
+ *                           every taken move's reverse.  Off the permissible
+ *                           pairs both carry the inputs' bits through.
+ *                           w_out == w01 and alt_out == w_alt (in place) are
+ *                           allowed, no other overlap
+ *   ll0_out  [batch]        the score of w01 (nullable)
+ *   ll_out   [batch]        the score of w_out, as ll0 + sum_e c[e]
+ *   gain_out [batch][S][S]  each pair's gain at its visit, taken or not; +0.0
+ *                           off the permissible pairs (nullable)
+ *   nacc_out [batch]        moves taken (nullable)
+ * cap as for nemo_score.  NEMO_F64 contexts only (NEMO_F32: NEMO_ERR_ARG);
+ * factored models at every S, generic and row-shared tables, wide ones
+ * included (no products of exp(T) are taken); E <= NEMO_EDGE_SWEEP_MAX_E
+ * (else NEMO_ERR_ARG).  No option routes the call: the two-pass forward
+ * (order weights into the context's scratch), then one block per evaluation.
+ * Every sum has a fixed order that depends on the staged model alone: an
+ * evaluation's bits depend neither on the batch, nor on its slot in it, nor on
+ * the run.  The host entry wants w_alt finite within [0, 1] and thr not NaN at
+ * the permissible pairs (else NEMO_ERR_ARG; it does not look elsewhere); on
+ * the _dev entry a NaN threshold never takes its move.
+ * _dev: enqueue only; after nemo_reserve(max_batch, .) with batch <=
+ * max_batch it neither allocates nor synchronises (else NEMO_ERR_STATE). */
+int nemo_edge_sweep(nemo_ctx* ctx, int batch, const int32_t* pos, const double* w01, const double* w_alt,
+                    const double* thr, int cap, double* w_out, double* alt_out, double* ll0_out, double* ll_out,
+                    double* gain_out, int32_t* nacc_out);
+int nemo_edge_sweep_dev(nemo_ctx* ctx, int batch, const int32_t* d_pos, const double* d_w01,
+                        const double* d_w_alt, const double* d_thr, int cap, double* d_w_out, double* d_alt_out,
+                        double* d_ll0, double* d_ll, double* d_gain, int32_t* d_nacc, void* stream);
 
 /* ---- the error rates as parameters: score and gradient in per-gene A_k, B_k --
  * The closing comment of nem.py ("shared probability between clusters for the

@@ -982,6 +982,87 @@ int nemo_score_moves(nemo_ctx* ctx, int batch, const int32_t* pos, const double*
   return NEMO_OK;
 }
 
+// ---- one sweep over the single-weight moves, each taken or not in turn (nemo_sweep.hip) ----
+static int sweep_refusals(const Ctx& c, int batch, int cap) {
+  if (c.dtype != NEMO_F64)
+    return fail(NEMO_ERR_ARG, "nemo_edge_sweep: dtype f32 (NEMO_F32) context; the sweep is fp64 only (NEMO_F64)");
+  if (batch < 0 || cap < 0) return fail(NEMO_ERR_ARG, "batch=%d cap=%d", batch, cap);
+  if (c.E > NEMO_EDGE_SWEEP_MAX_E)
+    return fail(NEMO_ERR_ARG, "nemo_edge_sweep: E=%d > %d (NEMO_EDGE_SWEEP_MAX_E: one block holds an evaluation's effects)",
+                c.E, NEMO_EDGE_SWEEP_MAX_E);
+  return NEMO_OK;
+}
+
+int nemo_edge_sweep_dev(nemo_ctx* ctx, int batch, const int32_t* d_pos, const double* d_w01, const double* d_w_alt,
+                        const double* d_thr, int cap, double* d_w_out, double* d_alt_out, double* d_ll0,
+                        double* d_ll, double* d_gain, int32_t* d_nacc, void* stream) {
+  int rc = check_ctx(ctx, true);
+  if (rc) return rc;
+  Ctx& c = ctx->c;
+  if ((rc = sweep_refusals(c, batch, cap))) return rc;
+  if (batch == 0) return NEMO_OK;
+  if (batch > c.cap_batch) return fail(NEMO_ERR_STATE, "batch %d > reserved %d", batch, c.cap_batch);
+  if (!d_pos || !d_w01 || !d_w_alt || !d_thr || !d_w_out || !d_alt_out || !d_ll)
+    return fail(NEMO_ERR_ARG, "null device pointer");
+  if (c.score_path == 2 && !c.factored)
+    return fail(NEMO_ERR_STATE, "score_path=2 (factored) but the staged table is not factorable");
+  hipStream_t st = pick(ctx, stream);
+  const bool fact = use_factored(c);
+  double* ll0 = d_ll0 ? d_ll0 : c.d_ll;
+  if ((rc = forward_ow(c, fact, batch, cap, d_pos, d_w01, ll0, st))) return rc;
+  HIPCHK(nemo::launch_edge_sweep(c, batch, cap, fact, d_pos, d_w01, d_w_alt, d_thr, ll0, d_w_out, d_alt_out, d_ll,
+                                 d_gain, d_nacc, st));
+  return NEMO_OK;
+}
+
+int nemo_edge_sweep(nemo_ctx* ctx, int batch, const int32_t* pos, const double* w01, const double* w_alt,
+                    const double* thr, int cap, double* w_out, double* alt_out, double* ll0_out, double* ll_out,
+                    double* gain_out, int32_t* nacc_out) {
+  int rc = check_ctx(ctx, true);
+  if (rc) return rc;
+  Ctx& c = ctx->c;
+  if ((rc = sweep_refusals(c, batch, cap))) return rc;
+  if (batch == 0) return NEMO_OK;
+  if (!pos || !w01 || !w_alt || !thr || !w_out || !alt_out || !ll_out) return fail(NEMO_ERR_ARG, "null host pointer");
+  if ((rc = check_pos(pos, batch, c.S))) return rc;
+  const size_t SS = (size_t)c.S * c.S;
+  if (const size_t bad = nemo::host::check_w_alt(pos, w_alt, batch, c.S, cap)) {
+    const size_t k = bad - 1;
+    return fail(NEMO_ERR_ARG, "nemo_edge_sweep: w_alt[%zu][%zu][%zu] = %g is not finite within [0, 1]", k / SS,
+                (k % SS) / c.S, k % c.S, w_alt[k]);
+  }
+  if (const size_t bad = nemo::host::check_sweep_thr(pos, thr, batch, c.S, cap)) {
+    const size_t k = bad - 1;
+    return fail(NEMO_ERR_ARG, "nemo_edge_sweep: thr[%zu][%zu][%zu] is NaN", k / SS, (k % SS) / c.S, k % c.S);
+  }
+  if ((rc = nemo_reserve(ctx, batch, 0))) return rc;
+  hipStream_t st = c.stream;
+  // the host entry's own temporaries: thresholds [batch][S][S], then the swept ll
+  // and the counts [batch] (the device entry needs none: nemo_reserve is as it was)
+  double* d_thr = nullptr;
+  HIPCHK(hipMallocAsync((void**)&d_thr, (batch * SS + 2 * (size_t)batch) * 8, st));
+  double* d_sll = d_thr + batch * SS;
+  int32_t* d_nacc = (int32_t*)(d_sll + batch);
+  HIPCHK(hipMemcpyAsync(c.d_pos, pos, batch * (size_t)c.S * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(c.d_w01, w01, batch * SS * 8, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(c.d_walt, w_alt, batch * SS * 8, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(d_thr, thr, batch * SS * 8, hipMemcpyHostToDevice, st));
+  // in place on the device (d_grad: the host entries run one at a time and end synchronised)
+  rc = nemo_edge_sweep_dev(ctx, batch, c.d_pos, c.d_w01, c.d_walt, d_thr, cap, c.d_w01, c.d_walt, c.d_ll, d_sll,
+                           c.d_grad, d_nacc, st);
+  if (rc == NEMO_OK) {
+    HIPCHK(hipMemcpyAsync(w_out, c.d_w01, batch * SS * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(alt_out, c.d_walt, batch * SS * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(ll_out, d_sll, batch * 8, hipMemcpyDeviceToHost, st));
+    if (ll0_out) HIPCHK(hipMemcpyAsync(ll0_out, c.d_ll, batch * 8, hipMemcpyDeviceToHost, st));
+    if (gain_out) HIPCHK(hipMemcpyAsync(gain_out, c.d_grad, batch * SS * 8, hipMemcpyDeviceToHost, st));
+    if (nacc_out) HIPCHK(hipMemcpyAsync(nacc_out, d_nacc, batch * 4, hipMemcpyDeviceToHost, st));
+  }
+  HIPCHK(hipFreeAsync(d_thr, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return rc;
+}
+
 // ---- ll, d ll / d (A_k, B_k) and d ll / d w01 at per-evaluation rates (nemo_grad.hip) ----
 static int rates_refusals(const Ctx& c) {
   if (c.dtype != NEMO_F64)

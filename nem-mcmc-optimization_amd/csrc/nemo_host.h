@@ -67,6 +67,24 @@ inline size_t check_w_alt(const int32_t* pos, const double* w_alt, int batch, in
   return 0;
 }
 
+// nemo_edge_sweep's argument check: thr [batch][S][S] must not be NaN at the
+// permissible pairs (+-inf are decisions: never / always) and is not looked at
+// elsewhere.  Returns 0, or 1 + the flat index of the first offending entry.
+inline size_t check_sweep_thr(const int32_t* pos, const double* thr, int batch, int S, int cap) {
+  if (cap >= S - 1) cap = 0;
+  for (int b = 0; b < batch; ++b) {
+    const int32_t* pb = pos + (size_t)b * S;
+    for (int i = 0; i < S; ++i)
+      for (int j = 0; j < S; ++j) {
+        const int d = pb[i] - pb[j];
+        if (d <= 0 || (cap > 0 && d > cap)) continue;
+        const size_t k = ((size_t)b * S + i) * S + j;
+        if (thr[k] != thr[k]) return k + 1;
+      }
+  }
+  return 0;
+}
+
 // ---------------------------------------------------------------------------
 // Staging validation: the factored form of a score table
 // ---------------------------------------------------------------------------

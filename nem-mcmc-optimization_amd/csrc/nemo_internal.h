@@ -9,6 +9,7 @@
 #include <string>
 #include <vector>
 
+#include "nemo.h"
 #include "nemo_host.h"
 
 namespace nemo {
@@ -746,6 +747,22 @@ hipError_t launch_score_moves_fused(Ctx& c, int batch, int cap, const int32_t* d
 hipError_t launch_moves_reduce(Ctx& c, int batch, int cap, bool factored, const int32_t* d_pos,
                                const double* d_w01, const double* d_walt, const double* d_ow, double* d_dll,
                                hipStream_t st);
+// ---- one sequential sweep over the single-weight moves (nemo_sweep.hip) ----
+// after the forward left ll0 and the order weights in d_ow: one block per
+// evaluation visits the permissible pairs in order (child position ascending,
+// then parent position), scores each move at the current state and takes it
+// when the gain exceeds thr.  The block size follows from E alone; a thread owns
+// at most kSweepMaxE / 1024 effects (nemo.h NEMO_EDGE_SWEEP_MAX_E)
+constexpr int kSweepMaxE = NEMO_EDGE_SWEEP_MAX_E;
+constexpr int kSweepTargetNpt = 4;  // effects per thread the block size aims at
+inline int sweep_threads(int E) {
+  int t = kWave;
+  while (t < 1024 && t * kSweepTargetNpt < E) t *= 2;
+  return t;
+}
+hipError_t launch_edge_sweep(Ctx& c, int batch, int cap, bool factored, const int32_t* d_pos, const double* d_w01,
+                             const double* d_walt, const double* d_thr, const double* d_ll0, double* d_wout,
+                             double* d_altout, double* d_ll, double* d_gain, int32_t* d_nacc, hipStream_t st);
 // the fused step's prep in ONE launch: prep_kernel's parent and pair lists
 // with the info rows preset to -1, and prep_factored_kernel's Delta / G / perm
 hipError_t launch_step_prep(Ctx& c, int batch, int cap, const int32_t* d_pos, const double* d_w01,

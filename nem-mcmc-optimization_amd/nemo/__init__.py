@@ -10,7 +10,7 @@ from . import generator, utils
 from .nem import NEM, TableModel
 
 __all__ = ["NEM", "TableModel", "generator", "utils", "Engine", "NEMOrderMCMC", "ExactArithmeticWarning",
-           "GreedyMethod", "greedy_flips"]
+           "GreedyMethod", "greedy_flips", "SweepMethod", "sweep_flips", "gibbs_edges"]
 
 
 def __getattr__(name):
@@ -24,7 +24,7 @@ def __getattr__(name):
     if name == "NEMOrderMCMC":
         from .nem_order_mcmc import NEMOrderMCMC
         return NEMOrderMCMC
-    if name in ("GreedyMethod", "greedy_flips"):
+    if name in ("GreedyMethod", "greedy_flips", "SweepMethod", "sweep_flips", "gibbs_edges"):
         from . import methods
         return getattr(methods, name)
     raise AttributeError(name)

@@ -234,6 +234,42 @@ class Engine:
         check(_lib.load().nemo_score_moves_dev(self._ctx, int(batch), d_pos, d_w01, d_w_alt, int(cap), d_ll, d_dll,
                                                stream))
 
+    # -- one sweep over the single-weight moves, each taken or not in turn --------
+    def edge_sweep(self, pos, w01, w_alt, thr, cap: int = 0):
+        """One sequential sweep over the permissible pairs of every order
+        (children by order position, then parents by order position): each
+        pair's move w01[b, i, j] -> w_alt[b, i, j] is scored exactly at the
+        CURRENT state and taken iff its gain exceeds thr[b, i, j] (+inf never,
+        -inf always).  -> (w_out, alt_out, ll0 (B,), ll (B,), gain (B, S, S),
+        nacc (B,)): w_out holds w_alt where the move was taken, alt_out the
+        value it replaced (a call on (w_out, alt_out) proposes the reverse
+        moves), ll0 / ll the scores of w01 / w_out, gain each pair's gain at
+        its visit (exactly 0 off the permissible pairs), nacc the moves taken.
+        ``w_alt`` must lie in [0, 1] and ``thr`` must not be NaN at the
+        permissible pairs; neither is read elsewhere (fp64 engines only)."""
+        pos = i32(np.atleast_2d(pos))
+        b = pos.shape[0]
+        w01 = f64(w01).reshape(b, self.S, self.S)
+        w_alt = f64(w_alt).reshape(b, self.S, self.S)
+        thr = f64(thr).reshape(b, self.S, self.S)
+        w_out = np.empty((b, self.S, self.S))
+        alt_out = np.empty((b, self.S, self.S))
+        ll0, ll = np.empty(b), np.empty(b)
+        gain = np.empty((b, self.S, self.S))
+        nacc = np.empty(b, dtype=np.int32)
+        a = _lib.addr
+        check(_lib.load().nemo_edge_sweep(self._ctx, b, a(pos), a(w01), a(w_alt), a(thr), int(cap), a(w_out),
+                                          a(alt_out), a(ll0), a(ll), a(gain), a(nacc)))
+        return w_out, alt_out, ll0, ll, gain, nacc
+
+    def edge_sweep_dev(self, batch, d_pos, d_w01, d_w_alt, d_thr, d_w_out, d_alt_out, d_ll, d_ll0=None, d_gain=None,
+                       d_nacc=None, cap=0, stream=None):
+        """Enqueue ``edge_sweep`` on device pointers (no sync; ``reserve`` the
+        batch first).  ``d_w_out`` may be ``d_w01`` and ``d_alt_out`` may be
+        ``d_w_alt`` (in place); a NaN threshold never takes its move."""
+        check(_lib.load().nemo_edge_sweep_dev(self._ctx, int(batch), d_pos, d_w01, d_w_alt, d_thr, int(cap), d_w_out,
+                                              d_alt_out, d_ll0, d_ll, d_gain, d_nacc, stream))
+
     # -- the error rates as parameters ------------------------------------------
     def score_rates(self, pos, w01, A, B, cap: int = 0, want_grad_w: bool = True):
         """Order scores at per-gene error rates, with their derivatives, on an

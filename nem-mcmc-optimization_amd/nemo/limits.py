@@ -36,6 +36,9 @@ MAX_PARTS = 64            # csrc/nemo_internal.h kExactMaxParts
 MAX_E_EXACT_GENERIC = NUMPY_BUFSIZE
 MAX_ABS_T_EXACT_GENERIC = 670.0
 MAX_ABS_U_EXACT_GENERIC = 700.0
+# Engine.edge_sweep: one block holds an evaluation's effects in its registers,
+# 16 per thread of 1024 (include/nemo.h NEMO_EDGE_SWEEP_MAX_E: the same value)
+MAX_E_EDGE_SWEEP = 16384
 
 
 def pairwise_parts(E: int):

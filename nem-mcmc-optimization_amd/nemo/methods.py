@@ -282,4 +282,111 @@ class GreedyMethod(_Base):
         return (1 * (weights[0] > 0.5)).T, float(ll[0])
 
 
-__all__ = ["InverseMethod", "Method", "JointMethod", "GreedyMethod", "greedy_flips", "INVERSE_BOUNDS", "GAMMA_BOUNDS"]
+def _permissible(pos, cap):
+    ok = pos[:, :, None] > pos[:, None, :]
+    if 0 < cap < pos.shape[1] - 1:
+        ok &= pos[:, :, None] - pos[:, None, :] <= cap
+    return ok
+
+
+def sweep_flips(engine, pos, weights, cap=0, max_sweeps=None, min_gain=1e-9, ll_trace=None):
+    """Coordinate ascent over the DAGs of fixed orders by single-edge flips, B
+    problems at once: every iteration is ONE ``engine.edge_sweep`` call with
+    ``w_alt = 1 - w`` and ``thr = min_gain``, which visits every permissible
+    pair in turn and takes each flip that gains more than ``min_gain`` at the
+    state the earlier flips of the same sweep left.  The loop ends when a sweep
+    takes nothing in every problem -- then no single flip gains more than
+    ``min_gain``, ``greedy_flips``' own stop rule -- or after ``max_sweeps``
+    sweeps (default S * S).  -> (weights (B, S, S), ll (B,), n_flips (B,),
+    n_sweeps); ll is the last sweep's score of the returned weights.
+    ``ll_trace``: a list that receives the (B,) ll before the first sweep and
+    after every sweep."""
+    pos = np.ascontiguousarray(np.atleast_2d(pos), dtype=np.int32)
+    b, s = pos.shape
+    w = np.array(weights, dtype=np.float64).reshape(b, s, s)
+    if not np.isin(w, (0.0, 1.0)).all():
+        raise ValueError("sweep_flips: weights must be 0 or 1")
+    max_sweeps = s * s if max_sweeps is None else int(max_sweeps)
+    thr = np.full((b, s, s), float(min_gain))
+    n_flips = np.zeros(b, dtype=np.int64)
+    n_sweeps = 0
+    ll = None
+    while n_sweeps < max_sweeps:
+        w, _, ll0, ll, _, nacc = engine.edge_sweep(pos, w, 1.0 - w, thr, cap=cap)
+        if ll_trace is not None:
+            if n_sweeps == 0:
+                ll_trace.append(np.array(ll0))
+            ll_trace.append(np.array(ll))
+        n_sweeps += 1
+        n_flips += nacc
+        if not np.any(nacc):
+            break
+    if ll is None:      # max_sweeps = 0: the score of the start (a sweep that takes nothing)
+        _, _, ll, _, _, _ = engine.edge_sweep(pos, w, 1.0 - w, np.full((b, s, s), np.inf), cap=cap)
+    return w, np.array(ll), n_flips, n_sweeps
+
+
+def gibbs_edges(engine, pos, weights, n_sweeps, beta=1.0, log_prior_odds=0.0, burn_in=0, rng=None, cap=0):
+    """Systematic-scan Gibbs sampler over the 0/1 DAGs of fixed orders, B chains
+    at once, target proportional to exp(beta ll + log_prior_odds * edges).
+
+    Every sweep is ONE ``engine.edge_sweep`` call with ``w_alt = 1 - w``: the
+    host draws u ~ U(0, 1) per pair and sets thr = (logit(u) - s rho) / beta, s
+    = +1 where the move switches the edge on and -1 where it switches it off --
+    u < sigmoid(beta gain + s rho), the edge's full conditional, solved for the
+    gain.  -> (weights (B, S, S), ll (n_sweeps, B), edge_prob (B, S, S));
+    edge_prob is the Rao-Blackwellised marginal: the mean over the sweeps from
+    ``burn_in`` on of sigmoid(beta (ll(edge on) - ll(edge off)) + rho), each
+    edge's conditional at its visit, and 0 off the permissible pairs.  beta ->
+    inf gives thr = 0, ``sweep_flips``' decision: annealing is a loop over this
+    call.  ``rng``: a seed or a numpy Generator."""
+    pos = np.ascontiguousarray(np.atleast_2d(pos), dtype=np.int32)
+    b, s = pos.shape
+    w = np.array(weights, dtype=np.float64).reshape(b, s, s)
+    if not np.isin(w, (0.0, 1.0)).all():
+        raise ValueError("gibbs_edges: weights must be 0 or 1")
+    if not beta > 0.0:
+        raise ValueError("gibbs_edges: beta must be positive")
+    rng = np.random.default_rng(rng)
+    ok = _permissible(pos, cap)
+    rho, beta = float(log_prior_odds), float(beta)
+    lls = np.empty((int(n_sweeps), b))
+    prob = np.zeros((b, s, s))
+    kept = 0
+    for k in range(int(n_sweeps)):
+        u = rng.random((b, s, s))
+        sign = np.where(w < 0.5, 1.0, -1.0)
+        with np.errstate(divide="ignore"):
+            thr = ((np.log(u) - np.log1p(-u)) - sign * rho) / beta
+        thr[~ok] = 0.0
+        w, _, _, lls[k], gain, _ = engine.edge_sweep(pos, w, 1.0 - w, thr, cap=cap)
+        if k >= burn_in:
+            z = beta * sign * gain + rho
+            prob += np.where(ok, 0.5 * (1.0 + np.tanh(0.5 * z)), 0.0)
+            kept += 1
+    return w, lls, prob / max(kept, 1)
+
+
+class SweepMethod(_Base):
+    """Coordinate ascent over the DAGs of one fixed order, every iteration one
+    ``nemo_edge_sweep`` call (``sweep_flips``).  There is no reference
+    counterpart in methods.py; the constructor, ``ll_list`` and ``optimize``'s
+    return follow ``GreedyMethod``."""
+
+    def optimize(self, start=None, max_sweeps=None):
+        """-> (weights.T, ll).  ``start``: a 0/1 weight matrix (default all
+        zeros; entries off the permissible pairs are dropped).  ``ll_list``
+        holds the ll at the start and after every sweep."""
+        w = np.zeros((self.num_s, self.num_s)) if start is None else np.asarray(start, dtype=np.float64) * self.mask
+        trace = []
+        weights, ll, n, sweeps = sweep_flips(self.engine, self._pos[None, :], w[None], max_sweeps=max_sweeps,
+                                             ll_trace=trace)
+        self.ll_list = [float(v[0]) for v in trace]
+        self.n_flips = int(n[0])
+        self.n_sweeps = int(sweeps)
+        print(f"Sweep LL: {float(ll[0])} after {self.n_flips} flips in {self.n_sweeps} sweeps")
+        return (1 * (weights[0] > 0.5)).T, float(ll[0])
+
+
+__all__ = ["InverseMethod", "Method", "JointMethod", "GreedyMethod", "greedy_flips", "SweepMethod", "sweep_flips",
+           "gibbs_edges", "INVERSE_BOUNDS", "GAMMA_BOUNDS"]
