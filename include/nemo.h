@@ -196,6 +196,47 @@ int nemo_score_moves(nemo_ctx* ctx, int batch, const int32_t* pos, const double*
 int nemo_score_moves_dev(nemo_ctx* ctx, int batch, const int32_t* d_pos, const double* d_w01,
                          const double* d_w_alt, int cap, double* d_ll, double* d_dll, void* stream);
 
+/* ---- exact score change of every single-node relocation of an order --------
+ * What order MCMC with node relocation (Kuipers & Moffa) or a greedy search
+ * over orders asks: what does the score become if node a moves to position q
+ * and everything else keeps its relative order?  The state is (order, W) with a
+ * FULL weight matrix: W[i][j] is the weight pair (i, j) carries whenever j
+ * precedes i.  Moving a from position p to q > p, the nodes m at positions
+ * p+1 .. q lose parent a and a gains them all; to q < p, the nodes m at q ..
+ * p-1 gain parent a and a loses them all.  With f_ij(e) = 1 - w_ij + w_ij
+ * exp(T[i][j][e]), z = cell - cs and ow = exp(z), in closed form
+ *   ll(a moved to q) - ll = sum_e log(1 + X_aq(e)),
+ *   q > p: X = -ow[a] + sum_m ow[m] (1 / f_ma - 1) + exp(z_a + sum_m log f_am)
+ *   q < p: X = -ow[a] + sum_m ow[m] (f_ma - 1)     + exp(z_a - sum_m log f_am)
+ * and both sums grow by one term per step away from p: the S - 1 targets of a
+ * node are one walk.  The factors of a are carried as a sum of logs (never a
+ * running product) and no exp overflows, so no model is refused for the range
+ * of its table.  No reference counterpart runs, so "exact" / "exact_dev" /
+ * "fact_kernel" do not route this call.
+ *   w01      [batch][S][S]  read at EVERY off-diagonal entry: the current
+ *                           weight at the permissible pairs, elsewhere the
+ *                           weight the pair takes when a relocation makes it
+ *                           permissible; the diagonal is never read
+ *   ll_out   [batch]        as nemo_score_grad: nemo_score(pos, w01) of the state
+ *   dll_out  [batch][S][S]  dll[a][q] = the score after moving NODE a to
+ *                           POSITION q, minus ll; every entry is written and
+ *                           dll[a][pos[a]] is exactly +0.0
+ * cap must cut nothing: 0 or >= S - 1 (else NEMO_ERR_ARG).  NEMO_F64 contexts
+ * only (NEMO_F32: NEMO_ERR_ARG); factored models at every S, generic and
+ * row-shared tables, wide ones included.  Two passes for every model: the
+ * forward with cells and cs into the context's scratch, then one block per
+ * (evaluation, node); no scratch beyond nemo_score's.  Every sum has a fixed
+ * order that depends on the staged model alone: an evaluation's bits depend
+ * neither on the batch, nor on its slot in it, nor on the run.  The host entry
+ * wants the off-diagonal entries of w01 finite within [0, 1] (else
+ * NEMO_ERR_ARG).  _dev: enqueue only; after nemo_reserve(max_batch, .) with
+ * batch <= max_batch it neither allocates nor synchronises (else
+ * NEMO_ERR_STATE). */
+int nemo_score_relocations(nemo_ctx* ctx, int batch, const int32_t* pos, const double* w01, int cap,
+                           double* ll_out, double* dll_out);
+int nemo_score_relocations_dev(nemo_ctx* ctx, int batch, const int32_t* d_pos, const double* d_w01, int cap,
+                               double* d_ll, double* d_dll, void* stream);
+
 /* ---- one sweep over the single-weight moves, each taken or not in turn -----
  * nemo_score_moves scores every move at ONE state; once a move is taken every
  * other score is stale.  This call walks the permissible pairs in sequence and
@@ -470,6 +511,11 @@ int nemo_real_sweep(nemo_ctx* ctx, int nprob, const int32_t* pos, const double* 
  *                two-pass path always (tests, A/B measurement)
  *   "moves_path_used" (get only) the path the last nemo_score_moves(_dev) ran:
  *                1 two-pass, 2 fused; 0 before any call
+ *   "reloc_path" 0 (default) auto, 1 = the two-pass path always.  Auto takes
+ *                the two-pass path for every model: a fused kernel measured no
+ *                faster, so both values run the same code
+ *   "reloc_path_used" (get only) the path the last nemo_score_relocations(_dev)
+ *                ran: 1 two-pass; 0 before any call
  *   "factored"   (get only) 1 if the staged table is factorable
  *   "win"        (get only) 1 if the capped lookup-table kernel is staged
  *                (U - U[S] two-valued per row, partial sums in range)
@@ -588,7 +634,8 @@ int nemo_real_sweep(nemo_ctx* ctx, int nprob, const int32_t* pos, const double* 
  *   "timing_kernel" 0 (default): nemo_timing_enable / _read time the score
  *                kernels; 1: the exact local optima's kernel (bench.py);
  *                2: nemo_real_sweep's pair solves (tools/real_score_time.py);
- *                3: nemo_score_moves' kernels (tools/moves_bench.py)
+ *                3: nemo_score_moves' kernels (tools/moves_bench.py);
+ *                4: nemo_score_relocations' kernels (tools/reloc_bench.py)
  *   "anc_overlap" 1 (default): nemo_optimal_weights_w makes ancestor_x on a
  *                second stream beside eval #1 (same bits); 0 = in line */
 int nemo_set_option(nemo_ctx* ctx, const char* name, int value);

@@ -982,6 +982,76 @@ int nemo_score_moves(nemo_ctx* ctx, int batch, const int32_t* pos, const double*
   return NEMO_OK;
 }
 
+// ---- ll(node a moved to position q) - ll of every (a, q) at a fixed full W (nemo_reloc.hip) ----
+static int reloc_refusals(const Ctx& c, int batch, int cap) {
+  if (c.dtype != NEMO_F64)
+    return fail(NEMO_ERR_ARG,
+                "nemo_score_relocations: dtype f32 (NEMO_F32) context; the relocation scores are fp64 only (NEMO_F64)");
+  if (batch < 0 || cap < 0) return fail(NEMO_ERR_ARG, "batch=%d cap=%d", batch, cap);
+  if (cap > 0 && cap < c.S - 1)
+    return fail(NEMO_ERR_ARG, "nemo_score_relocations: cap=%d cuts parent lists (0 or >= S - 1 = %d only)", cap,
+                c.S - 1);
+  return NEMO_OK;
+}
+
+int nemo_score_relocations_dev(nemo_ctx* ctx, int batch, const int32_t* d_pos, const double* d_w01, int cap,
+                               double* d_ll, double* d_dll, void* stream) {
+  int rc = check_ctx(ctx, true);
+  if (rc) return rc;
+  Ctx& c = ctx->c;
+  if ((rc = reloc_refusals(c, batch, cap))) return rc;
+  if (batch == 0) return NEMO_OK;
+  if (batch > c.cap_batch) return fail(NEMO_ERR_STATE, "batch %d > reserved %d", batch, c.cap_batch);
+  if (!d_pos || !d_w01 || !d_ll || !d_dll) return fail(NEMO_ERR_ARG, "null device pointer");
+  if (c.score_path == 2 && !c.factored)
+    return fail(NEMO_ERR_STATE, "score_path=2 (factored) but the staged table is not factorable");
+  hipStream_t st = pick(ctx, stream);
+  const bool fact = use_factored(c);
+  // (option reloc_path: auto and 1 take the same path today, nemo.h)
+  // the two-pass forward with the cells (in the order weights' scratch) and cs
+  if (fact) {
+    const int fk = c.fact_kernel;
+    c.fact_kernel = 1;  // option fact_kernel does not route this call
+    const hipError_t e = nemo::launch_score_factored(c, batch, 0, d_pos, d_w01, d_ll, c.d_cs, c.d_ow, nullptr, st);
+    c.fact_kernel = fk;
+    HIPCHK(e);
+  } else {
+    HIPCHK(nemo::launch_prep(c, batch, 0, d_pos, d_w01, c.d_rows, c.d_sw, c.d_cnt, nullptr, st));
+    HIPCHK(nemo::launch_score(c, batch, c.d_rows, c.d_sw, c.d_cnt, d_ll, c.d_cs, c.d_ow, nullptr, st));
+  }
+  c.ow_chains = 0;  // d_ow no longer holds fused-step order weights
+  HIPCHK(nemo::launch_reloc_reduce(c, batch, fact, d_pos, d_w01, c.d_ow, c.d_cs, d_dll, st));
+  c.reloc_path_used = 1;
+  return NEMO_OK;
+}
+
+int nemo_score_relocations(nemo_ctx* ctx, int batch, const int32_t* pos, const double* w01, int cap, double* ll_out,
+                           double* dll_out) {
+  int rc = check_ctx(ctx, true);
+  if (rc) return rc;
+  Ctx& c = ctx->c;
+  if ((rc = reloc_refusals(c, batch, cap))) return rc;
+  if (batch == 0) return NEMO_OK;
+  if (!pos || !w01 || !ll_out || !dll_out) return fail(NEMO_ERR_ARG, "null host pointer");
+  if ((rc = check_pos(pos, batch, c.S))) return rc;
+  if (const size_t bad = nemo::host::check_w_full(w01, batch, c.S)) {
+    const size_t k = bad - 1, SS = (size_t)c.S * c.S;
+    return fail(NEMO_ERR_ARG, "nemo_score_relocations: w01[%zu][%zu][%zu] = %g is not finite within [0, 1]", k / SS,
+                (k % SS) / c.S, k % c.S, w01[k]);
+  }
+  if ((rc = nemo_reserve(ctx, batch, 0))) return rc;
+  const size_t S = c.S;
+  hipStream_t st = c.stream;
+  HIPCHK(hipMemcpyAsync(c.d_pos, pos, batch * S * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(c.d_w01, w01, batch * S * S * 8, hipMemcpyHostToDevice, st));
+  // (d_grad: the host entries run one at a time and end synchronised)
+  if ((rc = nemo_score_relocations_dev(ctx, batch, c.d_pos, c.d_w01, cap, c.d_ll, c.d_grad, st))) return rc;
+  HIPCHK(hipMemcpyAsync(ll_out, c.d_ll, batch * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(dll_out, c.d_grad, batch * S * S * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return NEMO_OK;
+}
+
 // ---- one sweep over the single-weight moves, each taken or not in turn (nemo_sweep.hip) ----
 static int sweep_refusals(const Ctx& c, int batch, int cap) {
   if (c.dtype != NEMO_F64)
@@ -1985,9 +2055,10 @@ int nemo_set_option(nemo_ctx* ctx, const char* name, int value) {
     return NEMO_OK;
   }
   if (strcmp(name, "timing_kernel") == 0) {
-    if (value < 0 || value > 3)
+    if (value < 0 || value > 4)
       return fail(NEMO_ERR_ARG,
-                  "timing_kernel %d (0 score kernels, 1 exact local optima, 2 real-score pair solves, 3 move scores)",
+                  "timing_kernel %d (0 score kernels, 1 exact local optima, 2 real-score pair solves, 3 move scores, "
+                  "4 relocation scores)",
                   value);
     ctx->c.timing_kernel = value;
     return NEMO_OK;
@@ -2049,6 +2120,11 @@ int nemo_set_option(nemo_ctx* ctx, const char* name, int value) {
     ctx->c.grad_path = value;
     return NEMO_OK;
   }
+  if (strcmp(name, "reloc_path") == 0) {
+    if (value < 0 || value > 1) return fail(NEMO_ERR_ARG, "reloc_path=%d not in {0,1}", value);
+    ctx->c.reloc_path = value;
+    return NEMO_OK;
+  }
   if (strcmp(name, "moves_path") == 0) {
     if (value < 0 || value > 1) return fail(NEMO_ERR_ARG, "moves_path=%d not in {0,1}", value);
     ctx->c.moves_path = value;
@@ -2073,6 +2149,8 @@ int nemo_get_option(nemo_ctx* ctx, const char* name, int* value) {
   else if (strcmp(name, "grad_path_used") == 0) *value = c.grad_path_used;
   else if (strcmp(name, "moves_path") == 0) *value = c.moves_path;
   else if (strcmp(name, "moves_path_used") == 0) *value = c.moves_path_used;
+  else if (strcmp(name, "reloc_path") == 0) *value = c.reloc_path;
+  else if (strcmp(name, "reloc_path_used") == 0) *value = c.reloc_path_used;
   else if (strcmp(name, "factored") == 0) *value = c.factored ? 1 : 0;
   else if (strcmp(name, "fact_kernel") == 0) *value = c.fact_kernel;
   else if (strcmp(name, "i8o") == 0) *value = c.i8o_ok ? (c.i8o_diag ? 2 : 1) : 0;

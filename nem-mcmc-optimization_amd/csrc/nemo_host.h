@@ -85,6 +85,22 @@ inline size_t check_sweep_thr(const int32_t* pos, const double* thr, int batch, 
   return 0;
 }
 
+// nemo_score_relocations' argument check: w01 [batch][S][S] is a FULL weight
+// matrix, read at every off-diagonal entry, so each must be finite within [0,
+// 1]; the diagonal is not looked at.  Returns 0, or 1 + the flat index of the
+// first offending entry.
+inline size_t check_w_full(const double* w01, int batch, int S) {
+  for (int b = 0; b < batch; ++b)
+    for (int i = 0; i < S; ++i)
+      for (int j = 0; j < S; ++j) {
+        if (i == j) continue;
+        const size_t k = ((size_t)b * S + i) * S + j;
+        const double v = w01[k];
+        if (!(v >= 0.0 && v <= 1.0)) return k + 1;  // (NaN fails both comparisons)
+      }
+  return 0;
+}
+
 // ---------------------------------------------------------------------------
 // Staging validation: the factored form of a score table
 // ---------------------------------------------------------------------------

@@ -130,6 +130,11 @@ struct Ctx {
   double* d_walt = nullptr;        // [cap][S][S] the host entry's alternative weights
   double* d_movep = nullptr;       // [cap][grad_parts][moves_part_doubles] the fused kernel's partial sums by pair slot
   double* d_movell = nullptr;      // [cap][grad_parts] its partial ll
+  // exact score change of every single-node relocation (nemo_reloc.hip): option
+  // "reloc_path" 0 auto, 1 = always two-pass (auto takes the two-pass path for
+  // every model today); reloc_path_used: the last call's
+  int reloc_path = 0;
+  int reloc_path_used = 0;
 
   // score and gradient in per-gene error rates (nemo_score_rates): what
   // nemo_stage_knockdown keeps of D itself.  D's own words, not a flip flag per
@@ -747,6 +752,12 @@ hipError_t launch_score_moves_fused(Ctx& c, int batch, int cap, const int32_t* d
 hipError_t launch_moves_reduce(Ctx& c, int batch, int cap, bool factored, const int32_t* d_pos,
                                const double* d_w01, const double* d_walt, const double* d_ow, double* d_dll,
                                hipStream_t st);
+// ---- exact score change of every single-node relocation (nemo_reloc.hip) ----
+// dll[b][a][q] = ll(node a moved to position q) - ll at a fixed full weight
+// matrix, +0.0 at q = pos[a]: the second pass, after the two-pass forward left
+// the cells [batch][S+1][E] and cs [batch][E] (no scratch of its own)
+hipError_t launch_reloc_reduce(Ctx& c, int batch, bool factored, const int32_t* d_pos, const double* d_w01,
+                               const double* d_cells, const double* d_cs, double* d_dll, hipStream_t st);
 // ---- one sequential sweep over the single-weight moves (nemo_sweep.hip) ----
 // after the forward left ll0 and the order weights in d_ow: one block per
 // evaluation visits the permissible pairs in order (child position ascending,

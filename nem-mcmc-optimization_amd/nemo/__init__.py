@@ -10,7 +10,8 @@ from . import generator, utils
 from .nem import NEM, TableModel
 
 __all__ = ["NEM", "TableModel", "generator", "utils", "Engine", "NEMOrderMCMC", "ExactArithmeticWarning",
-           "GreedyMethod", "greedy_flips", "SweepMethod", "sweep_flips", "gibbs_edges"]
+           "GreedyMethod", "greedy_flips", "SweepMethod", "sweep_flips", "gibbs_edges", "apply_relocation",
+           "greedy_relocations", "gibbs_orders"]
 
 
 def __getattr__(name):
@@ -24,7 +25,8 @@ def __getattr__(name):
     if name == "NEMOrderMCMC":
         from .nem_order_mcmc import NEMOrderMCMC
         return NEMOrderMCMC
-    if name in ("GreedyMethod", "greedy_flips", "SweepMethod", "sweep_flips", "gibbs_edges"):
+    if name in ("GreedyMethod", "greedy_flips", "SweepMethod", "sweep_flips", "gibbs_edges", "apply_relocation",
+                "greedy_relocations", "gibbs_orders"):
         from . import methods
         return getattr(methods, name)
     raise AttributeError(name)

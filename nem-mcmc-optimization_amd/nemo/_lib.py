@@ -48,6 +48,8 @@ SIGNATURES = [
     ("nemo_score_grad_dev", C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp]),
     ("nemo_score_moves", C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp]),  # addr()
     ("nemo_score_moves_dev", C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp]),
+    ("nemo_score_relocations", C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp]),  # addr()
+    ("nemo_score_relocations_dev", C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp]),
     # (ctx, batch, pos, w01, w_alt, thr, cap, w_out, alt_out, ll0, ll, gain, nacc[, stream])
     ("nemo_edge_sweep", C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),  # addr()
     ("nemo_edge_sweep_dev", C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

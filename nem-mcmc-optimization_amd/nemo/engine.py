@@ -234,6 +234,30 @@ class Engine:
         check(_lib.load().nemo_score_moves_dev(self._ctx, int(batch), d_pos, d_w01, d_w_alt, int(cap), d_ll, d_dll,
                                                stream))
 
+    # -- the exact score change of every single-node relocation of an order -------
+    def score_relocations(self, pos, w01, cap: int = 0):
+        """Order scores and the exact change of each under every single-node
+        relocation at a fixed FULL weight matrix: (ll (B,), dll (B, S, S)),
+        dll[b, a, q] = the score after moving node a to position q (everything
+        else keeps its relative order), minus ll[b]; dll[b, a, pos[b, a]] is
+        exactly 0 (fp64 engines only).  ``w01`` is read at every off-diagonal
+        entry: w01[b, i, j] is the weight pair (i, j) carries whenever j
+        precedes i.  ``cap`` must cut nothing (0 or >= S - 1)."""
+        pos = i32(np.atleast_2d(pos))
+        b = pos.shape[0]
+        w01 = f64(w01).reshape(b, self.S, self.S)
+        ll = np.empty(b)
+        dll = np.empty((b, self.S, self.S))
+        a = _lib.addr
+        check(_lib.load().nemo_score_relocations(self._ctx, b, a(pos), a(w01), int(cap), a(ll), a(dll)))
+        return ll, dll
+
+    def score_relocations_dev(self, batch, d_pos, d_w01, d_ll, d_dll, cap=0, stream=None):
+        """Enqueue ``score_relocations`` on device pointers (no sync;
+        ``reserve`` the batch first)."""
+        check(_lib.load().nemo_score_relocations_dev(self._ctx, int(batch), d_pos, d_w01, int(cap), d_ll, d_dll,
+                                                     stream))
+
     # -- one sweep over the single-weight moves, each taken or not in turn --------
     def edge_sweep(self, pos, w01, w_alt, thr, cap: int = 0):
         """One sequential sweep over the permissible pairs of every order

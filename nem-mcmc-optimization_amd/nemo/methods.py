@@ -388,5 +388,112 @@ class SweepMethod(_Base):
         return (1 * (weights[0] > 0.5)).T, float(ll[0])
 
 
+def apply_relocation(pos, a, q):
+    """The order positions after node ``a`` moves to position ``q`` and every
+    other node keeps its relative order (pure numpy).  ``pos`` (S,) with scalar
+    ``a``, ``q``, or (B, S) with (B,) arrays: one relocation per row.  The nodes
+    between the old and the new position shift by one towards the old one."""
+    pos = np.asarray(pos)
+    out = np.array(np.atleast_2d(pos), dtype=pos.dtype)
+    a = np.atleast_1d(np.asarray(a, dtype=np.int64))
+    q = np.atleast_1d(np.asarray(q, dtype=np.int64))
+    rows = np.arange(out.shape[0])
+    p = out[rows, a].astype(np.int64)[:, None]
+    qq = q[:, None]
+    down = (out > p) & (out <= qq)       # q > p: positions p+1 .. q move down by one
+    up = (out >= qq) & (out < p)         # q < p: positions q .. p-1 move up by one
+    out = out - down.astype(out.dtype) + up.astype(out.dtype)
+    out[rows, a] = q
+    return out[0] if pos.ndim == 1 else out
+
+
+def greedy_relocations(engine, pos, weights, max_iter=None, min_gain=1e-9, ll_trace=None):
+    """Hill-climb over ORDERS at a fixed full weight matrix by single-node
+    relocations, B problems at once.
+
+    ``pos`` (B, S) order positions, ``weights`` (B, S, S) full weight matrices
+    (weights[b, i, j]: the weight of pair (i, j) whenever j precedes i).  Every
+    iteration is ONE ``engine.score_relocations`` call over all B problems.  Each
+    problem applies its best (node a, position q) if that gains more than
+    ``min_gain`` (ties: the lowest (a, q)), else it is finished; the loop ends
+    when every problem is finished or after ``max_iter`` iterations (default S *
+    S).  -> (pos (B, S), ll (B,), n_moves (B,)); ll is that of a final
+    ``score_relocations`` call on the returned orders, not a running sum.
+    ``ll_trace``: a list that receives the (B,) ll of every call."""
+    pos = np.array(np.atleast_2d(pos), dtype=np.int32)
+    b, s = pos.shape
+    w = np.ascontiguousarray(np.asarray(weights, dtype=np.float64).reshape(b, s, s))
+    max_iter = s * s if max_iter is None else int(max_iter)
+    n_moves = np.zeros(b, dtype=np.int64)
+    active = np.ones(b, dtype=bool)
+    rows = np.arange(b)
+    it = 0
+    while True:
+        ll, dll = engine.score_relocations(pos, w)
+        if ll_trace is not None:
+            ll_trace.append(np.array(ll))
+        if it >= max_iter:
+            return pos, np.array(ll), n_moves
+        gain = np.asarray(dll).reshape(b, s * s)
+        best = gain.argmax(axis=1)          # the first maximum: the lowest (a, q)
+        active &= gain[rows, best] > min_gain
+        if not active.any():                # nothing moves: this call's ll is the final one
+            return pos, np.array(ll), n_moves
+        a, q = np.divmod(best, s)
+        pos[active] = apply_relocation(pos[active], a[active], q[active])
+        n_moves += active
+        it += 1
+
+
+def gibbs_orders(engine, pos, weights, n_sweeps, beta=1.0, burn_in=0, rng=None):
+    """Systematic-scan Gibbs sampler over ORDERS at a fixed full weight matrix
+    by node relocation (Kuipers & Moffa), B chains at once, target proportional
+    to exp(beta ll(order)).
+
+    For each node a in label order, ONE ``engine.score_relocations`` call over
+    all B chains gives the score of every position of a; the host draws a's new
+    position from its full conditional p(q) proportional to exp(beta dll[a, q])
+    by inverse CDF from one uniform per chain and applies it.  -> (pos (B, S),
+    ll (n_sweeps * S, B), before (B, S, S)): ll[k * S + a] is the score of the
+    order each chain holds after sweep k's draw of node a (the call's ll plus
+    the drawn entry of dll); before[b, i, j] is the Rao-Blackwellised marginal
+    P(j precedes i): the mean, over the sweeps from ``burn_in`` on and over the
+    visits of i and of j, of the visited node's conditional probability of
+    landing on the matching side of the other (0 on the diagonal).  ``rng``: a
+    seed or a numpy Generator."""
+    pos = np.array(np.atleast_2d(pos), dtype=np.int32)
+    b, s = pos.shape
+    w = np.ascontiguousarray(np.asarray(weights, dtype=np.float64).reshape(b, s, s))
+    if not beta > 0.0:
+        raise ValueError("gibbs_orders: beta must be positive")
+    rng = np.random.default_rng(rng)
+    beta = float(beta)
+    rows = np.arange(b)
+    lls = np.empty((int(n_sweeps) * s, b))
+    before = np.zeros((b, s, s))
+    kept = 0
+    for k in range(int(n_sweeps)):
+        for a in range(s):
+            ll, dll = engine.score_relocations(pos, w)
+            g = beta * np.asarray(dll)[:, a, :]
+            pq = np.exp(g - g.max(axis=1, keepdims=True))
+            cdf = np.cumsum(pq, axis=1)
+            u = rng.random(b)
+            q = np.minimum((cdf < (u * cdf[:, -1])[:, None]).sum(axis=1), s - 1)
+            if k >= burn_in:
+                # rank of every other node with a taken out; j precedes a iff a lands past it
+                rank = pos - (pos > pos[:, a][:, None])
+                above = 1.0 - cdf[rows[:, None], rank] / cdf[:, -1][:, None]   # P(q > rank_j)
+                above[:, a] = 0.0
+                before[:, a, :] += above
+                below = 1.0 - above
+                below[:, a] = 0.0
+                before[:, :, a] += below
+            lls[k * s + a] = np.asarray(ll) + np.asarray(dll)[rows, a, q]
+            pos = apply_relocation(pos, np.full(b, a), q)
+        kept += k >= burn_in
+    return pos, lls, before / max(2 * kept, 1)
+
+
 __all__ = ["InverseMethod", "Method", "JointMethod", "GreedyMethod", "greedy_flips", "SweepMethod", "sweep_flips",
-           "gibbs_edges", "INVERSE_BOUNDS", "GAMMA_BOUNDS"]
+           "gibbs_edges", "apply_relocation", "greedy_relocations", "gibbs_orders", "INVERSE_BOUNDS", "GAMMA_BOUNDS"]
