@@ -287,6 +287,62 @@ int nemo_edge_sweep_dev(nemo_ctx* ctx, int batch, const int32_t* d_pos, const do
                         const double* d_w_alt, const double* d_thr, int cap, double* d_w_out, double* d_alt_out,
                         double* d_ll0, double* d_ll, double* d_gain, int32_t* d_nacc, void* stream);
 
+/* ---- relocations walked in sequence: a Gibbs or greedy sweep over orders -----
+ * nemo_score_relocations scores every relocation at ONE order; once one is
+ * taken every other score is stale.  This call walks a list of node visits per
+ * evaluation inside one launch and keeps the state exact.  The state is (order,
+ * W) with a full weight matrix as for nemo_score_relocations: w01 is read at
+ * every off-diagonal entry and never changes; the diagonal is never read.
+ * Visit k of evaluation b, a = visit[b][k] at its current position p:
+ *   row       r[q] = ll(a moved to q) - ll at the CURRENT order, by
+ *             nemo_score_relocations' closed form (the exponent a sum of logs,
+ *             no exp overflows); r[p] is exactly +0.0
+ *   Gibbs     (beta finite, > 0) g = beta r, pq[q] = exp(g[q] - max g), cdf the
+ *             running sum of pq over q ascending, added sequentially;
+ *             q* = min(#{q : cdf[q] < u cdf[S-1]}, S - 1): u = 0 lands on
+ *             position 0 and u >= 1 on S - 1
+ *   greedy    (beta = +inf) q* the position of the largest r[q], ties to the
+ *             lowest q, taken only if r[q*] > min_gain, strictly, else q* = p;
+ *             u is not read and may be null
+ *   update    for q* != p the order changes; for every effect each passed
+ *             node's cell takes -+log f_ma, a's cell +-sum_m log f_am, and cs[e]
+ *             is formed afresh as the log-sum-exp of the updated column (rows 0
+ *             .. S ascending, the maximum subtracted)
+ * A row that holds a NaN leaves q* = p on the device entry.
+ *   visit      [batch][nvisit]     node labels in [0, S), any number of times each
+ *   u          [batch][nvisit]     one uniform per visit (Gibbs)
+ *   pos_out    [batch][S]          the final order; pos_out == pos (in place)
+ *                                  is allowed, no other overlap
+ *   ll0_out    [batch]             the score of the initial state (nullable)
+ *   ll_out     [batch]             the score of the final state, sum_e cs[e]
+ *   q_out      [batch][nvisit]     the position each visited node took (nullable)
+ *   dll_out    [batch][nvisit][S]  the row r of each visit (nullable)
+ *   ll_vis_out [batch][nvisit]     the score held after each visit; a visit that
+ *                                  moved nothing carries the previous bits (nullable)
+ *   nmoved_out [batch]             moves taken (nullable)
+ * cap must cut nothing: 0 or >= S - 1; nvisit >= 0; beta > 0; min_gain >= 0
+ * (else NEMO_ERR_ARG).  nvisit = 0 scores the state and copies pos through.
+ * NEMO_F64 contexts only (NEMO_F32: NEMO_ERR_ARG); factored models at every S
+ * <= 256, generic and row-shared tables, wide ones included.  No option routes
+ * the call ("exact" / "exact_dev" / "fact_kernel" included): the two-pass
+ * forward with cells and cs into the context's scratch, then one block per
+ * evaluation; E is not bounded.  Every sum has a fixed order that depends on S
+ * and E alone: an evaluation's bits, and hence its decisions, depend neither on
+ * the batch, nor on its slot in it, nor on the run.  The host entry wants pos a
+ * permutation, the off-diagonal entries of w01 finite within [0, 1], visit
+ * within [0, S) and, in Gibbs mode, u finite and >= 0 (else NEMO_ERR_ARG with
+ * the offending index; no refused call writes any output).
+ * _dev: enqueue only; after nemo_reserve(max_batch, .) with batch <=
+ * max_batch it neither allocates nor synchronises (else NEMO_ERR_STATE). */
+int nemo_order_sweep(nemo_ctx* ctx, int batch, const int32_t* pos, const double* w01, int nvisit,
+                     const int32_t* visit, const double* u, double beta, double min_gain, int cap,
+                     int32_t* pos_out, double* ll0_out, double* ll_out, int32_t* q_out, double* dll_out,
+                     double* ll_vis_out, int32_t* nmoved_out);
+int nemo_order_sweep_dev(nemo_ctx* ctx, int batch, const int32_t* d_pos, const double* d_w01, int nvisit,
+                         const int32_t* d_visit, const double* d_u, double beta, double min_gain, int cap,
+                         int32_t* d_pos_out, double* d_ll0, double* d_ll, int32_t* d_q, double* d_dll,
+                         double* d_ll_vis, int32_t* d_nmoved, void* stream);
+
 /* ---- the error rates as parameters: score and gradient in per-gene A_k, B_k --
  * The closing comment of nem.py ("shared probability between clusters for the
  * error rates, use that as a latent variable") names what the reference never
@@ -635,7 +691,8 @@ int nemo_real_sweep(nemo_ctx* ctx, int nprob, const int32_t* pos, const double* 
  *                kernels; 1: the exact local optima's kernel (bench.py);
  *                2: nemo_real_sweep's pair solves (tools/real_score_time.py);
  *                3: nemo_score_moves' kernels (tools/moves_bench.py);
- *                4: nemo_score_relocations' kernels (tools/reloc_bench.py)
+ *                4: nemo_score_relocations' kernels (tools/reloc_bench.py);
+ *                5: nemo_order_sweep's kernel (tools/order_sweep_bench.py)
  *   "anc_overlap" 1 (default): nemo_optimal_weights_w makes ancestor_x on a
  *                second stream beside eval #1 (same bits); 0 = in line */
 int nemo_set_option(nemo_ctx* ctx, const char* name, int value);

@@ -1133,6 +1133,117 @@ int nemo_edge_sweep(nemo_ctx* ctx, int batch, const int32_t* pos, const double* 
   return rc;
 }
 
+// ---- relocations walked in sequence, each drawn or taken in turn (nemo_order_sweep.hip) ----
+static int order_sweep_refusals(const Ctx& c, int batch, int nvisit, double beta, double min_gain, int cap) {
+  if (c.dtype != NEMO_F64)
+    return fail(NEMO_ERR_ARG, "nemo_order_sweep: dtype f32 (NEMO_F32) context; the sweep is fp64 only (NEMO_F64)");
+  if (batch < 0 || cap < 0 || nvisit < 0) return fail(NEMO_ERR_ARG, "batch=%d cap=%d nvisit=%d", batch, cap, nvisit);
+  if (cap > 0 && cap < c.S - 1)
+    return fail(NEMO_ERR_ARG, "nemo_order_sweep: cap=%d cuts parent lists (0 or >= S - 1 = %d only)", cap, c.S - 1);
+  if (!(beta > 0.0)) return fail(NEMO_ERR_ARG, "nemo_order_sweep: beta=%g (> 0; +inf: greedy)", beta);
+  if (!(min_gain >= 0.0)) return fail(NEMO_ERR_ARG, "nemo_order_sweep: min_gain=%g (>= 0)", min_gain);
+  return NEMO_OK;
+}
+
+int nemo_order_sweep_dev(nemo_ctx* ctx, int batch, const int32_t* d_pos, const double* d_w01, int nvisit,
+                         const int32_t* d_visit, const double* d_u, double beta, double min_gain, int cap,
+                         int32_t* d_pos_out, double* d_ll0, double* d_ll, int32_t* d_q, double* d_dll,
+                         double* d_ll_vis, int32_t* d_nmoved, void* stream) {
+  int rc = check_ctx(ctx, true);
+  if (rc) return rc;
+  Ctx& c = ctx->c;
+  if ((rc = order_sweep_refusals(c, batch, nvisit, beta, min_gain, cap))) return rc;
+  if (batch == 0) return NEMO_OK;
+  if (batch > c.cap_batch) return fail(NEMO_ERR_STATE, "batch %d > reserved %d", batch, c.cap_batch);
+  const bool gibbs = std::isfinite(beta);
+  if (!d_pos || !d_w01 || !d_pos_out || !d_ll || (nvisit > 0 && (!d_visit || (gibbs && !d_u))))
+    return fail(NEMO_ERR_ARG, "null device pointer");
+  if (c.score_path == 2 && !c.factored)
+    return fail(NEMO_ERR_STATE, "score_path=2 (factored) but the staged table is not factorable");
+  hipStream_t st = pick(ctx, stream);
+  const bool fact = use_factored(c);
+  // the two-pass forward with the cells (in the order weights' scratch) and cs, as nemo_score_relocations_dev
+  if (fact) {
+    const int fk = c.fact_kernel;
+    c.fact_kernel = 1;  // option fact_kernel does not route this call
+    const hipError_t e = nemo::launch_score_factored(c, batch, 0, d_pos, d_w01, c.d_ll, c.d_cs, c.d_ow, nullptr, st);
+    c.fact_kernel = fk;
+    HIPCHK(e);
+  } else {
+    HIPCHK(nemo::launch_prep(c, batch, 0, d_pos, d_w01, c.d_rows, c.d_sw, c.d_cnt, nullptr, st));
+    HIPCHK(nemo::launch_score(c, batch, c.d_rows, c.d_sw, c.d_cnt, c.d_ll, c.d_cs, c.d_ow, nullptr, st));
+  }
+  c.ow_chains = 0;  // d_ow no longer holds fused-step order weights
+  HIPCHK(nemo::launch_order_sweep(c, batch, fact, d_pos, d_w01, nvisit, d_visit, d_u, beta, min_gain, c.d_ow, c.d_cs,
+                                  d_pos_out, d_ll0, d_ll, d_q, d_dll, d_ll_vis, d_nmoved, st));
+  return NEMO_OK;
+}
+
+int nemo_order_sweep(nemo_ctx* ctx, int batch, const int32_t* pos, const double* w01, int nvisit,
+                     const int32_t* visit, const double* u, double beta, double min_gain, int cap, int32_t* pos_out,
+                     double* ll0_out, double* ll_out, int32_t* q_out, double* dll_out, double* ll_vis_out,
+                     int32_t* nmoved_out) {
+  int rc = check_ctx(ctx, true);
+  if (rc) return rc;
+  Ctx& c = ctx->c;
+  if ((rc = order_sweep_refusals(c, batch, nvisit, beta, min_gain, cap))) return rc;
+  if (batch == 0) return NEMO_OK;
+  const bool gibbs = std::isfinite(beta);
+  if (!pos || !w01 || !pos_out || !ll_out || (nvisit > 0 && (!visit || (gibbs && !u))))
+    return fail(NEMO_ERR_ARG, "null host pointer");
+  if ((rc = check_pos(pos, batch, c.S))) return rc;
+  const size_t S = c.S, SS = S * S, B = batch, NV = nvisit;
+  if (const size_t bad = nemo::host::check_w_full(w01, batch, c.S)) {
+    const size_t k = bad - 1;
+    return fail(NEMO_ERR_ARG, "nemo_order_sweep: w01[%zu][%zu][%zu] = %g is not finite within [0, 1]", k / SS,
+                (k % SS) / S, k % S, w01[k]);
+  }
+  if (const size_t bad = nemo::host::check_visit(visit, batch, nvisit, c.S)) {
+    const size_t k = bad - 1;
+    return fail(NEMO_ERR_ARG, "nemo_order_sweep: visit[%zu][%zu] = %d is not a node in [0, %d)", k / NV, k % NV,
+                (int)visit[k], c.S);
+  }
+  if (gibbs)
+    if (const size_t bad = nemo::host::check_sweep_u(u, batch, nvisit)) {
+      const size_t k = bad - 1;
+      return fail(NEMO_ERR_ARG, "nemo_order_sweep: u[%zu][%zu] = %g is not finite and >= 0", k / NV, k % NV, u[k]);
+    }
+  if ((rc = nemo_reserve(ctx, batch, 0))) return rc;
+  hipStream_t st = c.stream;
+  // the host entry's own temporaries in one allocation (the device entry needs none: nemo_reserve is
+  // as it was): doubles u, dll, ll_vis [batch][nvisit](.[S]), ll0, ll [batch]; then int32 visit, q
+  // [batch][nvisit], nmoved [batch]
+  const size_t nd = B * NV * (S + 2) + 2 * B, ni = 2 * B * NV + B;
+  double* d_u = nullptr;
+  HIPCHK(hipMallocAsync((void**)&d_u, nd * 8 + ni * 4, st));
+  double* d_dll = d_u + B * NV;
+  double* d_vis = d_dll + B * NV * S;
+  double* d_ll0 = d_vis + B * NV;
+  double* d_sll = d_ll0 + B;
+  int32_t* d_visit = (int32_t*)(d_sll + B);
+  int32_t* d_q = d_visit + B * NV;
+  int32_t* d_nm = d_q + B * NV;
+  HIPCHK(hipMemcpyAsync(c.d_pos, pos, B * S * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(c.d_w01, w01, B * SS * 8, hipMemcpyHostToDevice, st));
+  if (NV) HIPCHK(hipMemcpyAsync(d_visit, visit, B * NV * 4, hipMemcpyHostToDevice, st));
+  if (NV && gibbs) HIPCHK(hipMemcpyAsync(d_u, u, B * NV * 8, hipMemcpyHostToDevice, st));
+  // the order in place on the device
+  rc = nemo_order_sweep_dev(ctx, batch, c.d_pos, c.d_w01, nvisit, d_visit, d_u, beta, min_gain, cap, c.d_pos, d_ll0,
+                            d_sll, d_q, d_dll, d_vis, d_nm, st);
+  if (rc == NEMO_OK) {
+    HIPCHK(hipMemcpyAsync(pos_out, c.d_pos, B * S * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(ll_out, d_sll, B * 8, hipMemcpyDeviceToHost, st));
+    if (ll0_out) HIPCHK(hipMemcpyAsync(ll0_out, d_ll0, B * 8, hipMemcpyDeviceToHost, st));
+    if (nmoved_out) HIPCHK(hipMemcpyAsync(nmoved_out, d_nm, B * 4, hipMemcpyDeviceToHost, st));
+    if (NV && q_out) HIPCHK(hipMemcpyAsync(q_out, d_q, B * NV * 4, hipMemcpyDeviceToHost, st));
+    if (NV && dll_out) HIPCHK(hipMemcpyAsync(dll_out, d_dll, B * NV * S * 8, hipMemcpyDeviceToHost, st));
+    if (NV && ll_vis_out) HIPCHK(hipMemcpyAsync(ll_vis_out, d_vis, B * NV * 8, hipMemcpyDeviceToHost, st));
+  }
+  HIPCHK(hipFreeAsync(d_u, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return rc;
+}
+
 // ---- ll, d ll / d (A_k, B_k) and d ll / d w01 at per-evaluation rates (nemo_grad.hip) ----
 static int rates_refusals(const Ctx& c) {
   if (c.dtype != NEMO_F64)
@@ -2055,10 +2166,10 @@ int nemo_set_option(nemo_ctx* ctx, const char* name, int value) {
     return NEMO_OK;
   }
   if (strcmp(name, "timing_kernel") == 0) {
-    if (value < 0 || value > 4)
+    if (value < 0 || value > 5)
       return fail(NEMO_ERR_ARG,
                   "timing_kernel %d (0 score kernels, 1 exact local optima, 2 real-score pair solves, 3 move scores, "
-                  "4 relocation scores)",
+                  "4 relocation scores, 5 order sweeps)",
                   value);
     ctx->c.timing_kernel = value;
     return NEMO_OK;

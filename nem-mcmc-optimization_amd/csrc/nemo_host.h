@@ -101,6 +101,26 @@ inline size_t check_w_full(const double* w01, int batch, int S) {
   return 0;
 }
 
+// nemo_order_sweep's argument check: visit [batch][nvisit] holds node labels in
+// [0, S) (any number of times each).  Returns 0, or 1 + the flat index of the
+// first offending entry.
+inline size_t check_visit(const int32_t* visit, int batch, int nvisit, int S) {
+  const size_t n = (size_t)batch * (size_t)std::max(nvisit, 0);
+  for (size_t k = 0; k < n; ++k)
+    if (visit[k] < 0 || visit[k] >= S) return k + 1;
+  return 0;
+}
+
+// nemo_order_sweep's argument check in Gibbs mode: u [batch][nvisit], one
+// uniform per visit, must be finite and >= 0 (u >= 1 is a decision: the last
+// position).  Returns 0, or 1 + the flat index of the first offending entry.
+inline size_t check_sweep_u(const double* u, int batch, int nvisit) {
+  const size_t n = (size_t)batch * (size_t)std::max(nvisit, 0);
+  for (size_t k = 0; k < n; ++k)
+    if (!(u[k] >= 0.0 && u[k] <= 1.7976931348623157e308)) return k + 1;  // (NaN fails both comparisons)
+  return 0;
+}
+
 // ---------------------------------------------------------------------------
 // Staging validation: the factored form of a score table
 // ---------------------------------------------------------------------------

@@ -276,7 +276,8 @@ struct Ctx {
 
   // timing of the score kernel (timing_kernel 0) or of the exact local
   // optima's kernel (1) or of the real-score pair solves (2) or of the
-  // move-score kernels (3; option "timing_kernel")
+  // move-score kernels (3), the relocation scores (4) or the order sweep (5;
+  // option "timing_kernel")
   bool timing = false;
   int timing_kernel = 0;
   std::vector<hipEvent_t> ev_pool;
@@ -774,6 +775,16 @@ inline int sweep_threads(int E) {
 hipError_t launch_edge_sweep(Ctx& c, int batch, int cap, bool factored, const int32_t* d_pos, const double* d_w01,
                              const double* d_walt, const double* d_thr, const double* d_ll0, double* d_wout,
                              double* d_altout, double* d_ll, double* d_gain, int32_t* d_nacc, hipStream_t st);
+// ---- relocations walked in sequence inside one launch (nemo_order_sweep.hip) ----
+// after the two-pass forward left the cells [batch][S+1][E] and cs [batch][E]:
+// one block per evaluation owns its slice of both as mutable state, visits the
+// nodes of d_visit [batch][nvisit] in turn, scores each one's S positions at the
+// current order, chooses one (beta finite: a Gibbs draw from d_u; +inf: the best
+// gain above min_gain) and applies the move.  The block size follows from E alone
+hipError_t launch_order_sweep(Ctx& c, int batch, bool factored, const int32_t* d_pos, const double* d_w01, int nvisit,
+                              const int32_t* d_visit, const double* d_u, double beta, double min_gain, double* d_cells,
+                              double* d_cs, int32_t* d_posout, double* d_ll0, double* d_ll, int32_t* d_q,
+                              double* d_dll, double* d_llvis, int32_t* d_nmoved, hipStream_t st);
 // the fused step's prep in ONE launch: prep_kernel's parent and pair lists
 // with the info rows preset to -1, and prep_factored_kernel's Delta / G / perm
 hipError_t launch_step_prep(Ctx& c, int batch, int cap, const int32_t* d_pos, const double* d_w01,

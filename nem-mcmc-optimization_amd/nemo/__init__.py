@@ -11,7 +11,7 @@ from .nem import NEM, TableModel
 
 __all__ = ["NEM", "TableModel", "generator", "utils", "Engine", "NEMOrderMCMC", "ExactArithmeticWarning",
            "GreedyMethod", "greedy_flips", "SweepMethod", "sweep_flips", "gibbs_edges", "apply_relocation",
-           "greedy_relocations", "gibbs_orders"]
+           "greedy_relocations", "gibbs_orders", "sweep_relocations"]
 
 
 def __getattr__(name):
@@ -26,7 +26,7 @@ def __getattr__(name):
         from .nem_order_mcmc import NEMOrderMCMC
         return NEMOrderMCMC
     if name in ("GreedyMethod", "greedy_flips", "SweepMethod", "sweep_flips", "gibbs_edges", "apply_relocation",
-                "greedy_relocations", "gibbs_orders"):
+                "greedy_relocations", "gibbs_orders", "sweep_relocations"):
         from . import methods
         return getattr(methods, name)
     raise AttributeError(name)

@@ -53,6 +53,10 @@ SIGNATURES = [
     # (ctx, batch, pos, w01, w_alt, thr, cap, w_out, alt_out, ll0, ll, gain, nacc[, stream])
     ("nemo_edge_sweep", C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),  # addr()
     ("nemo_edge_sweep_dev", C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("nemo_order_sweep", C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp, C.c_double, C.c_double, C.c_int,
+                                   _vp, _vp, _vp, _vp, _vp, _vp, _vp]),  # addr()
+    ("nemo_order_sweep_dev", C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp, C.c_double, C.c_double, C.c_int,
+                                       _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("nemo_score_rates", C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp]),  # addr()
     ("nemo_score_rates_dev", C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp]),
     ("nemo_score_group_dev", C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp, _vp]),

@@ -294,6 +294,50 @@ class Engine:
         check(_lib.load().nemo_edge_sweep_dev(self._ctx, int(batch), d_pos, d_w01, d_w_alt, d_thr, int(cap), d_w_out,
                                               d_alt_out, d_ll0, d_ll, d_gain, d_nacc, stream))
 
+    # -- relocations walked in sequence, each drawn or taken in turn ----------------
+    def order_sweep(self, pos, w01, visit, u=None, beta: float = 1.0, min_gain: float = 0.0, cap: int = 0):
+        """A list of node visits per order walked in ONE call at a fixed FULL
+        weight matrix: at visit k node ``visit[b, k]`` has its S positions
+        scored exactly at the CURRENT order (``score_relocations``' row), one is
+        chosen and the move is applied.  ``beta`` finite: a Gibbs draw from
+        ``u[b, k]`` by inverse CDF over exp(beta row), positions ascending (u =
+        0: position 0, u >= 1: position S - 1).  ``beta = inf``: the best
+        position, ties to the lowest, taken only if it gains more than
+        ``min_gain``; ``u`` is not read.  -> (pos_out (B, S), ll0 (B,), ll
+        (B,), q (B, nvisit), dll (B, nvisit, S), ll_vis (B, nvisit), nmoved
+        (B,)): the final orders, the scores of the initial and final states, the
+        position each visited node took, each visit's row (exactly 0 at the
+        node's own position), the score held after each visit and the number of
+        moves taken (fp64 engines only; ``cap`` must cut nothing)."""
+        pos = i32(np.atleast_2d(pos))
+        b = pos.shape[0]
+        w01 = f64(w01).reshape(b, self.S, self.S)
+        visit = i32(np.asarray(visit))
+        nv = visit.size // max(b, 1)
+        visit = visit.reshape(b, nv)
+        if u is not None:
+            u = f64(u).reshape(b, nv)
+        pos_out = np.empty((b, self.S), dtype=np.int32)
+        ll0, ll = np.empty(b), np.empty(b)
+        q = np.empty((b, nv), dtype=np.int32)
+        dll = np.empty((b, nv, self.S))
+        ll_vis = np.empty((b, nv))
+        nmoved = np.empty(b, dtype=np.int32)
+        a = _lib.addr
+        check(_lib.load().nemo_order_sweep(self._ctx, b, a(pos), a(w01), nv, a(visit), None if u is None else a(u),
+                                           float(beta), float(min_gain), int(cap), a(pos_out), a(ll0), a(ll), a(q),
+                                           a(dll), a(ll_vis), a(nmoved)))
+        return pos_out, ll0, ll, q, dll, ll_vis, nmoved
+
+    def order_sweep_dev(self, batch, d_pos, d_w01, nvisit, d_visit, d_u, d_pos_out, d_ll, d_ll0=None, d_q=None,
+                        d_dll=None, d_ll_vis=None, d_nmoved=None, beta=1.0, min_gain=0.0, cap=0, stream=None):
+        """Enqueue ``order_sweep`` on device pointers (no sync; ``reserve`` the
+        batch first).  ``d_pos_out`` may be ``d_pos`` (in place); a row that
+        holds a NaN leaves its node where it is."""
+        check(_lib.load().nemo_order_sweep_dev(self._ctx, int(batch), d_pos, d_w01, int(nvisit), d_visit, d_u,
+                                               float(beta), float(min_gain), int(cap), d_pos_out, d_ll0, d_ll, d_q,
+                                               d_dll, d_ll_vis, d_nmoved, stream))
+
     # -- the error rates as parameters ------------------------------------------
     def score_rates(self, pos, w01, A, B, cap: int = 0, want_grad_w: bool = True):
         """Order scores at per-gene error rates, with their derivatives, on an

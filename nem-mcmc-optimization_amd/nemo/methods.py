@@ -445,7 +445,7 @@ def greedy_relocations(engine, pos, weights, max_iter=None, min_gain=1e-9, ll_tr
         it += 1
 
 
-def gibbs_orders(engine, pos, weights, n_sweeps, beta=1.0, burn_in=0, rng=None):
+def gibbs_orders(engine, pos, weights, n_sweeps, beta=1.0, burn_in=0, rng=None, fused=False):
     """Systematic-scan Gibbs sampler over ORDERS at a fixed full weight matrix
     by node relocation (Kuipers & Moffa), B chains at once, target proportional
     to exp(beta ll(order)).
@@ -460,7 +460,14 @@ def gibbs_orders(engine, pos, weights, n_sweeps, beta=1.0, burn_in=0, rng=None):
     P(j precedes i): the mean, over the sweeps from ``burn_in`` on and over the
     visits of i and of j, of the visited node's conditional probability of
     landing on the matching side of the other (0 on the diagonal).  ``rng``: a
-    seed or a numpy Generator."""
+    seed or a numpy Generator.
+
+    ``fused=True``: every sweep is ONE ``engine.order_sweep`` call that visits
+    the nodes in label order on the device, with the sweep's uniforms drawn as
+    ``rng.random((S, B))`` -- the stream S successive ``rng.random(B)`` consume --
+    so the chains are the unfused ones wherever no uniform falls within rounding
+    of a CDF step; ll comes from the call's per-visit scores and ``before`` from
+    its rows and the orders replayed from the positions taken."""
     pos = np.array(np.atleast_2d(pos), dtype=np.int32)
     b, s = pos.shape
     w = np.ascontiguousarray(np.asarray(weights, dtype=np.float64).reshape(b, s, s))
@@ -472,6 +479,30 @@ def gibbs_orders(engine, pos, weights, n_sweeps, beta=1.0, burn_in=0, rng=None):
     lls = np.empty((int(n_sweeps) * s, b))
     before = np.zeros((b, s, s))
     kept = 0
+    if fused:
+        if not np.isfinite(beta):
+            raise ValueError("gibbs_orders: beta must be finite")
+        visit = np.ascontiguousarray(np.broadcast_to(np.arange(s, dtype=np.int32), (b, s)))
+        for k in range(int(n_sweeps)):
+            u = np.ascontiguousarray(rng.random((s, b)).T)
+            pos_out, _, _, q, dll, ll_vis, _ = engine.order_sweep(pos, w, visit, u=u, beta=beta)
+            lls[k * s:(k + 1) * s] = np.asarray(ll_vis).T
+            for a in range(s):
+                if k >= burn_in:
+                    g = beta * np.asarray(dll)[:, a, :]
+                    pq = np.exp(g - g.max(axis=1, keepdims=True))
+                    cdf = np.cumsum(pq, axis=1)
+                    rank = pos - (pos > pos[:, a][:, None])
+                    above = 1.0 - cdf[rows[:, None], rank] / cdf[:, -1][:, None]
+                    above[:, a] = 0.0
+                    before[:, a, :] += above
+                    below = 1.0 - above
+                    below[:, a] = 0.0
+                    before[:, :, a] += below
+                pos = apply_relocation(pos, np.full(b, a), np.asarray(q)[:, a])
+            pos = np.array(pos_out, dtype=np.int32)
+            kept += k >= burn_in
+        return pos, lls, before / max(2 * kept, 1)
     for k in range(int(n_sweeps)):
         for a in range(s):
             ll, dll = engine.score_relocations(pos, w)
@@ -495,5 +526,40 @@ def gibbs_orders(engine, pos, weights, n_sweeps, beta=1.0, burn_in=0, rng=None):
     return pos, lls, before / max(2 * kept, 1)
 
 
+def sweep_relocations(engine, pos, weights, max_sweeps=None, min_gain=1e-9, ll_trace=None):
+    """Coordinate ascent over ORDERS at a fixed full weight matrix, B problems at
+    once: every iteration is ONE greedy ``engine.order_sweep`` call (``beta =
+    inf``) that visits the nodes in label order and moves each to its best
+    position if that gains more than ``min_gain`` at the order the earlier moves
+    of the same sweep left.  The loop ends when a sweep moves nothing in every
+    problem -- then no single relocation gains more than ``min_gain``,
+    ``greedy_relocations``' own stop rule -- or after ``max_sweeps`` sweeps
+    (default S * S).  -> (pos (B, S), ll (B,), n_moves (B,), n_sweeps); ll is
+    the last sweep's score of the returned orders.  ``ll_trace``: a list that
+    receives the (B,) ll before the first sweep and after every sweep."""
+    pos = np.array(np.atleast_2d(pos), dtype=np.int32)
+    b, s = pos.shape
+    w = np.ascontiguousarray(np.asarray(weights, dtype=np.float64).reshape(b, s, s))
+    max_sweeps = s * s if max_sweeps is None else int(max_sweeps)
+    visit = np.ascontiguousarray(np.broadcast_to(np.arange(s, dtype=np.int32), (b, s)))
+    n_moves = np.zeros(b, dtype=np.int64)
+    n_sweeps = 0
+    ll = None
+    while n_sweeps < max_sweeps:
+        pos, ll0, ll, _, _, _, nmoved = engine.order_sweep(pos, w, visit, beta=np.inf, min_gain=min_gain)
+        if ll_trace is not None:
+            if n_sweeps == 0:
+                ll_trace.append(np.array(ll0))
+            ll_trace.append(np.array(ll))
+        n_sweeps += 1
+        n_moves += nmoved
+        if not np.any(nmoved):
+            break
+    if ll is None:      # max_sweeps = 0: the score of the start (no visits)
+        _, _, ll, _, _, _, _ = engine.order_sweep(pos, w, visit[:, :0], beta=np.inf, min_gain=min_gain)
+    return np.array(pos, dtype=np.int32), np.array(ll), n_moves, n_sweeps
+
+
 __all__ = ["InverseMethod", "Method", "JointMethod", "GreedyMethod", "greedy_flips", "SweepMethod", "sweep_flips",
-           "gibbs_edges", "apply_relocation", "greedy_relocations", "gibbs_orders", "INVERSE_BOUNDS", "GAMMA_BOUNDS"]
+           "gibbs_edges", "apply_relocation", "greedy_relocations", "gibbs_orders", "sweep_relocations",
+           "INVERSE_BOUNDS", "GAMMA_BOUNDS"]
